@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the batched UHSDR SSB-RX chain on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|northstar]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|northstar] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one uhsdr_rx_process() call: every channel of this rank advances by one block of
@@ -11,9 +11,17 @@ lattice, WDSP AGC, biquads, interpolator, 6-stage anti-alias lattice, treble she
 scale), with inputs resident in HBM.  Ranks own disjoint channel ranges (weak scaling, no
 collective on the data path).  value = complex input samples of all ranks / max-rank time.
 
-Also reported: per-kernel device time from HIP events recorded on the library's stream over
-the timed region, the HBM roofline of the dominant kernel (algorithmic bytes per launch /
-mean launch time vs 8 TB/s), and the CPU oracle's throughput on the host (baseline only).
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the
+output dump when --dump-outputs is given, and the result line.
+
+--dump-outputs DIR: after the timed steps, what the last timed step wrote (the f32 audio, and
+with --dst the int32 codec frames) goes to DIR/<name>.npy.  The inputs depend only on the
+arguments, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else: per-kernel device time from HIP events recorded on the library's
+stream in a separate pass, the HBM roofline of the dominant kernel (algorithmic bytes per launch /
+mean launch time vs 8 TB/s), the 1M-channel north-star legs, the gather leg (N > 1), and the CPU
+oracle's throughput on the host (baseline only).
 """
 from __future__ import annotations
 
@@ -136,11 +144,38 @@ DEVICE_HANDOFF = 3       # --handoff: uhsdr_rx_set_pipelined's mode (event 1, de
 SCHEDULE_NAMES = {1: "split_pipe", 2: "split_fused", 3: "chain"}
 
 
+DUMP_MAX_BYTES = 60 * 1000 * 1000     # --dump-outputs: all files of a run together stay under 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(dump_dir, torch, rank, world, audio, dst):
+    """The outputs of the last timed step as DIR/<name>.npy: audio (f32) and, when written, the
+    int32 codec frames as float64 (exact).  Each rank writes its own files and has an equal share
+    of DUMP_MAX_BYTES; a batch past that share is cut to a fixed, seeded sample of its channels
+    (sorted; the same rows on every run of the same shape)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    C = audio.shape[0]
+    per_channel = audio[0].numel() * 4 + (dst[0].numel() * 8 if dst is not None else 0)
+    keep = max(1, DUMP_MAX_BYTES // max(world, 1) // per_channel)
+    rows = None
+    if C > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(C, size=keep, replace=False))
+        rows = torch.from_numpy(rows).to(audio.device)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dump_dir, f"audio{tag}.npy"),
+            (audio if rows is None else audio[rows]).cpu().numpy().astype(np.float32, copy=False))
+    if dst is not None:
+        np.save(os.path.join(dump_dir, f"dst{tag}.npy"),
+                (dst if rows is None else dst[rows]).cpu().numpy().astype(np.float64))
+
+
 def timed_run(U, synth, shard, torch, dist, dev, world, rank, C, N, steps, warmup, pool, want_dst, pipelined=False,
-              precision=0, schedule=None, front_block=0, reduce_dev=None, board=0, ensure_dist=None):
+              precision=0, schedule=None, front_block=0, reduce_dev=None, board=0, ensure_dist=None,
+              kernel_pass=True, dump_dir=None):
     """W untimed + K timed steps of one RxChain on this rank; returns (max-rank seconds,
-    per-kernel (total ms, launches) from HIP events on the library's stream, plan, finite, schedule,
-    device hand-off give-ups after the timed loop (uhsdr_rx_handoff_timeouts; 0 required))."""
+    per-kernel (total ms, launches) from HIP events on the library's stream (None without
+    `kernel_pass`), plan, finite, schedule, device hand-off give-ups after the timed loop
+    (uhsdr_rx_handoff_timeouts; 0 required)).  `dump_dir`: the last timed step's outputs go there."""
     cfg = U.default_config(board=board)
     stream = torch.cuda.current_stream(dev)
     chain = U.RxChain(cfg, channels=C, frames=N, stream=stream.cuda_stream, schedule=schedule)
@@ -172,6 +207,13 @@ def timed_run(U, synth, shard, torch, dist, dev, world, rank, C, N, steps, warmu
     # the device hand-off's failure contract (include/uhsdr.h): a poll that gave up poisons its call
     # and sets the handle's failure word; the timed calls count only if none did
     timeouts = chain.handoff_timeouts()
+    ok = bool(torch.isfinite(audio).all().item())
+    if dump_dir:
+        dump_outputs(dump_dir, torch, rank, world, audio, dst)
+    if not kernel_pass:
+        chain.close()
+        del inputs
+        return elapsed, None, plan, ok, sched, timeouts
     # per-kernel breakdown in a separate pass: HIP events on the library's own stream bracket
     # every kernel of every call (the records cost host time, so they never share a clock with
     # the throughput loop above)
@@ -186,7 +228,7 @@ def timed_run(U, synth, shard, torch, dist, dev, world, rank, C, N, steps, warmu
     torch.cuda.synchronize(dev)
     ktimes = chain.kernel_times()
     chain.enable_timing(False)
-    ok = bool(torch.isfinite(audio).all().item())
+    ok = ok and bool(torch.isfinite(audio).all().item())
     chain.close()
     del inputs
     return elapsed, ktimes, plan, ok, sched, timeouts
@@ -268,9 +310,17 @@ def main():
     ap.add_argument("--channels", type=int, default=0, help="override channels per GPU")
     ap.add_argument("--frames", type=int, default=0, help="override frames per call")
     ap.add_argument("--dst", action="store_true", help="also write int32 codec frames")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-northstar", action="store_true", help="skip the 1M-channel north-star leg")
-    ap.add_argument("--no-gather", action="store_true", help="skip the RCCL gather leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(audio, f32; with --dst also dst, the codec frames as f64); a batch past 60 MB (over all "
+                         "ranks) is cut to a fixed seeded sample of its channels")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the per-kernel event pass and the "
+                         "roofline, the north-star legs, the gather leg (N > 1) and the CPU baseline "
+                         "(each can be dropped again with its --no-* option)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline leg")
+    ap.add_argument("--no-northstar", action="store_true", help="--full without the 1M-channel north-star legs")
+    ap.add_argument("--no-gather", action="store_true", help="--full without the RCCL gather leg (N > 1)")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--serial", action="store_true",
                     help="run rx_front and rx_back of a call back to back on one stream instead of the "
@@ -345,11 +395,12 @@ def main():
                                                  args.warmup, max(1, args.pool), args.dst, pipelined, prec,
                                                  SCHEDULES[args.schedule], args.front_block, reduce_dev,
                                                  U.BOARD_MCHF if args.board == "mchf" else U.BOARD_OVI40,
-                                                 ensure_dist=ensure_dist)
+                                                 ensure_dist=ensure_dist, kernel_pass=args.full,
+                                                 dump_dir=args.dump_outputs)
     ensure_dist()
 
     gather = None
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         gs = max(10, args.steps // 4)
         gt = gather_run(U, synth, shard, torch, dist, dev, world, rank, C, N, gs, 5, args.dist_backend)
         gather = {"value": round(world * C * N * gs / gt / 1e6, 2), "unit": "Msamples/s", "steps": gs,
@@ -379,7 +430,7 @@ def main():
                 "schedule": n_sched, "outputs_finite": n_ok, "handoff_timeouts": n_tmo}
 
     ns = None
-    if world == 1 and not args.no_northstar and args.workload != "northstar" and not (args.channels or args.frames):
+    if args.full and world == 1 and not args.no_northstar and args.workload != "northstar" and not (args.channels or args.frames):
         ns = north_star_leg(prec)
         ns["precision"] = args.precision
         if prec == U.PRECISION_EXACT:
@@ -396,10 +447,6 @@ def main():
 
     total_samples = world * C * N * args.steps
     value = total_samples / elapsed / 1e6
-    ab = algorithmic_bytes(plan, C, N, args.dst)
-    roofline, kms = roofline_of(ab, ktimes, pmc_traffic(args.workload) if not (args.channels or args.frames) else None)
-    chain_dev_ms = sum(kms.values())
-    chain_gbs = ab["chain"] / (chain_dev_ms * 1e-3) / 1e9
     out = {
         "metric": "Msamples/s through full SSB-RX chain (node); % of HBM-roofline per GPU",
         "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
@@ -414,25 +461,30 @@ def main():
                    "pipelined": pipelined, "handoff": args.handoff if pipelined else None,
                    "precision": args.precision, "schedule": sched,
                    **({"board": "mchf"} if args.board == "mchf" else {})},
-        "roofline": roofline,
-        "chain": {"device_ms_per_step": round(chain_dev_ms, 5),
-                  "kernel_ms": {k: round(v, 5) for k, v in kms.items()},
-                  "alg_bytes_per_sample": round(ab["chain"] / (C * N), 2),
-                  "s_live_bytes_per_channel": ab["s_live_bytes"],
-                  "hbm_frac": round(ab["chain"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                  "hbm_frac_kernel_events": round(chain_gbs / HBM_PEAK_GBS, 4),
-                  "note": "C2 (4096 channels) is latency-bound: one lane per channel for the recursive "
-                          "stages leaves most of the 256 CUs idle; see DESIGN.md and north_star"
-                          + ("; pipelined: rx_front of the next call overlaps rx_back in the timed loop; the "
-                             "kernel event times come from a separate serial pass" if pipelined else "")},
         "outputs_finite": ok,
         "handoff_timeouts": timeouts,
     }
+    if args.full:
+        ab = algorithmic_bytes(plan, C, N, args.dst)
+        roofline, kms = roofline_of(ab, ktimes, pmc_traffic(args.workload) if not (args.channels or args.frames) else None)
+        chain_dev_ms = sum(kms.values())
+        chain_gbs = ab["chain"] / (chain_dev_ms * 1e-3) / 1e9
+        out["roofline"] = roofline
+        out["chain"] = {"device_ms_per_step": round(chain_dev_ms, 5),
+                        "kernel_ms": {k: round(v, 5) for k, v in kms.items()},
+                        "alg_bytes_per_sample": round(ab["chain"] / (C * N), 2),
+                        "s_live_bytes_per_channel": ab["s_live_bytes"],
+                        "hbm_frac": round(ab["chain"] / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                        "hbm_frac_kernel_events": round(chain_gbs / HBM_PEAK_GBS, 4),
+                        "note": "C2 (4096 channels) is latency-bound: one lane per channel for the recursive "
+                                "stages leaves most of the 256 CUs idle; see DESIGN.md and north_star"
+                                + ("; pipelined: rx_front of the next call overlaps rx_back in the timed loop; the "
+                                   "kernel event times come from a separate serial pass" if pipelined else "")}
     if ns:
         out["north_star"] = ns
     if gather:
         out["with_gather"] = gather
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(plan, N, args.cpu_budget)
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -50,7 +50,7 @@ def _last_json(out: str):
 
 def test_bench_gpus2_launches_two_ranks(cuda):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--no-northstar", "--no-cpu", "--dist-backend", "gloo"]
+           "--full", "--no-northstar", "--no-cpu", "--dist-backend", "gloo"]
     r = subprocess.run(cmd, env=_bench_env(), cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -61,6 +61,34 @@ def test_bench_gpus2_launches_two_ranks(cuda):
     # whole-job value counts both ranks' samples over the max-rank time
     per_call = 2 * d["config"]["channels_per_gpu"] * d["config"]["frames_per_call"]
     assert abs(d["value"] - per_call / d["ms_per_step"] / 1e3) / d["value"] < 0.01
+
+
+def test_bench_plain_run_dumps_last_step(cuda, tmp_path):
+    """A plain run (no --full) prints the headline line without the extra legs, and --dump-outputs
+    holds what the last timed step wrote: warm-up and timed steps both start at block 0 of the pool,
+    so the chain saw blocks 0, 0, 1, 2 and the dump is the oracle's last block, bit for bit."""
+    warmup, steps = 1, 3
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--channels", str(PER_RANK), "--frames", str(FRAMES), "--dst", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=_bench_env(), cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+    assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["outputs_finite"] and d["handoff_timeouts"] == 0
+    assert abs(d["value"] - PER_RANK * FRAMES / d["ms_per_step"] / 1e3) / d["value"] < 0.01
+    for leg in ("north_star", "cpu_baseline", "with_gather", "roofline", "chain"):
+        assert leg not in d, leg
+    audio = np.load(out / "audio.npy")
+    dst = np.load(out / "dst.npy")
+    assert audio.dtype == np.float32 and audio.shape == (PER_RANK, FRAMES)
+    assert dst.dtype == np.float64 and dst.shape == (PER_RANK, FRAMES, 2)
+    seq = [k for k in range(warmup)] + [k for k in range(steps)]
+    iq = np.concatenate([synth.ssb_iq_torch(0, PER_RANK, k * FRAMES, FRAMES, cuda).cpu().numpy() for k in seq], axis=1)
+    ref_a, ref_d = oracle.OracleRx(U.build_plan(U.default_config()), PER_RANK).process(iq, threads=8)
+    assert np.array_equal(audio.view(np.uint32), ref_a[:, -FRAMES:].view(np.uint32))
+    assert np.array_equal(dst, ref_d[:, -FRAMES:].astype(np.float64))
 
 
 def test_bench_world_mismatch_fails():

@@ -9,5 +9,6 @@ export TMPDIR=/tmp
 tag=${1:-a}
 timeout -k 10 200 python tools/host_cost.py > gpurun_out/host_cost_$tag.txt 2>&1 || { tail -20 gpurun_out/host_cost_$tag.txt; exit 1; }
 cat gpurun_out/host_cost_$tag.txt
-timeout -k 10 300 rocprofv3 --kernel-trace -d gpurun_out/tl_$tag -o tl --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu --no-northstar > gpurun_out/tl_$tag.log 2>&1 || { tail -20 gpurun_out/tl_$tag.log; exit 1; }
-python tools/c2_timeline.py gpurun_out/tl_$tag > gpurun_out/tl_$tag.txt && cat gpurun_out/tl_$tag.txt
+mkdir -p bench_out
+timeout -k 10 300 rocprofv3 --kernel-trace -d bench_out/tl_$tag -o tl --output-format csv -- python bench.py --full --steps 20 --warmup 5 --no-cpu --no-northstar > bench_out/tl_$tag.log 2>&1 || { tail -20 bench_out/tl_$tag.log; exit 1; }
+python tools/c2_timeline.py bench_out/tl_$tag > bench_out/tl_$tag.txt && cat bench_out/tl_$tag.txt

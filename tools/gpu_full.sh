@@ -14,21 +14,22 @@ tail -3 gpurun_out/pytest_gpu.log
 [ $rc -eq 0 ] || { echo "pytest gpu failed rc=$rc"; tail -60 gpurun_out/pytest_gpu.log; exit $rc; }
 step "smoke"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step "bench (default)"
-timeout -k 10 400 python bench.py > gpurun_out/bench_${tag}.json 2> gpurun_out/bench_${tag}.err || { tail -30 gpurun_out/bench_${tag}.err; exit 1; }
-cat gpurun_out/bench_${tag}.json
+step "bench (default, every leg)"
+mkdir -p bench_out
+timeout -k 10 400 python bench.py --full > bench_out/bench_${tag}.json 2> bench_out/bench_${tag}.err || { tail -30 bench_out/bench_${tag}.err; exit 1; }
+cat bench_out/bench_${tag}.json
 step "rocprof kernel trace c2"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c2_${tag} -o prof --output-format csv -- python bench.py --steps 200 --warmup 20 --no-cpu --no-northstar > gpurun_out/prof_c2_${tag}.log 2>&1 || { tail -20 gpurun_out/prof_c2_${tag}.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d bench_out/prof_c2_${tag} -o prof --output-format csv -- python bench.py --full --steps 200 --warmup 20 --no-cpu --no-northstar > bench_out/prof_c2_${tag}.log 2>&1 || { tail -20 bench_out/prof_c2_${tag}.log; exit 1; }
 step "rocprof kernel trace northstar"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_ns_${tag} -o prof --output-format csv -- python bench.py --workload northstar --steps 100 --warmup 10 --no-cpu > gpurun_out/prof_ns_${tag}.log 2>&1 || { tail -20 gpurun_out/prof_ns_${tag}.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d bench_out/prof_ns_${tag} -o prof --output-format csv -- python bench.py --full --workload northstar --steps 100 --warmup 10 --no-cpu > bench_out/prof_ns_${tag}.log 2>&1 || { tail -20 bench_out/prof_ns_${tag}.log; exit 1; }
 step "rocprof kernel trace northstar fma"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_nsfma_${tag} -o prof --output-format csv -- python bench.py --workload northstar --precision fma --steps 100 --warmup 10 --no-cpu > gpurun_out/prof_nsfma_${tag}.log 2>&1 || { tail -20 gpurun_out/prof_nsfma_${tag}.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d bench_out/prof_nsfma_${tag} -o prof --output-format csv -- python bench.py --full --workload northstar --precision fma --steps 100 --warmup 10 --no-cpu > bench_out/prof_nsfma_${tag}.log 2>&1 || { tail -20 bench_out/prof_nsfma_${tag}.log; exit 1; }
 step "pmc northstar"
-bash tools/gpu_pmc.sh ns_${tag} --workload northstar --steps 5 --warmup 2 || exit 1
+bash tools/gpu_pmc.sh ns_${tag} --full --workload northstar --steps 5 --warmup 2 || exit 1
 step "pmc northstar fma"
-bash tools/gpu_pmc.sh nsfma_${tag} --workload northstar --precision fma --steps 5 --warmup 2 || exit 1
+bash tools/gpu_pmc.sh nsfma_${tag} --full --workload northstar --precision fma --steps 5 --warmup 2 || exit 1
 step "pmc c2"
-bash tools/gpu_pmc.sh c2_${tag} --steps 20 --warmup 5 --no-northstar || exit 1
+bash tools/gpu_pmc.sh c2_${tag} --full --steps 20 --warmup 5 --no-northstar || exit 1
 python tools/pmc_summary.py ns_${tag} > gpurun_out/pmc_northstar_${tag}.json
 python tools/pmc_summary.py c2_${tag} > gpurun_out/pmc_c2_${tag}.json
 python tools/pmc_summary.py nsfma_${tag} > gpurun_out/pmc_northstar_fma_${tag}.json

@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC counter passes (one rocprofv3 --pmc run per counter group, kernel-trace only, no
 # sys/runtime trace) over a short bench run.  Usage: tools/gpu_pmc.sh <tag> <bench args...>
+# (--full among them: the counters then cover the serial per-kernel pass after the timed loop too)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
