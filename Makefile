@@ -67,7 +67,7 @@ clean:
 .PHONY: all ref clean
 
 # compile-time variants of libuhsdr_amd.so for A/B measurement (bench.py with UHSDR_LIB=<path>):
-#   make variant VTAG=w3 VFLAGS=-DUHSDR_FUSED_WAVES=3
+#   make variant VTAG=trace VFLAGS=-DUHSDR_TRACE
 # every HIP source is rebuilt with VFLAGS into its own object directory, so a flag read by any
 # source takes effect (VFLAGS=-Itools/isa builds only the P48 receive kernels: quick A/B builds;
 # VFLAGS comes first on the line, so its -I wins over csrc for uhsdr_rx_variants.inc)

@@ -18,7 +18,7 @@ MAX_INTERP = 16
 IQ_BLOCK_SIZE = 32
 FILTER_PATH_NUM = 87
 
-ABI_VERSION = 5   # include/uhsdr.h UHSDR_ABI_VERSION: checked against the library at load()
+ABI_VERSION = 6  # include/uhsdr.h UHSDR_ABI_VERSION: checked against the library at load()
 UHSDR_OK = 0
 UHSDR_ARGUMENT_ERROR = -1
 UHSDR_LENGTH_ERROR = -2
@@ -194,7 +194,6 @@ SIGNATURES = {
     "uhsdr_rx_get_schedule": (C.c_int32, [C.c_void_p]),
     "uhsdr_rx_handoff_timeouts": (C.c_int32, [C.c_void_p]),
     "uhsdr_rx_set_handoff_bound": (C.c_int, [C.c_void_p, C.c_uint32]),
-    "uhsdr_rx_debug_persist": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "uhsdr_rx_set_front_block": (C.c_int, [C.c_void_p, C.c_int32]),
     "uhsdr_rx_set_cw_outputs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhsdr_rx_cw_blocks_max": (C.c_int32, [C.c_void_p]),

@@ -16,12 +16,18 @@
 //    every window sample is read from LDS once per pass, coefficients come in via SGPRs.
 //
 //  rx_back   (sequential per channel: lane == channel, 64 channels per workgroup)
-//      wave 0: IIR lattice pre-filter -> WDSP AGC -> scale -> biquad_1 -> polyphase interp
-//      wave 1: anti-alias lattice -> biquad_2 -> line-out scale -> f32 / int32 codec frames
+//      IIR lattice pre-filter -> WDSP AGC -> scale -> biquad_1 -> polyphase interp ->
+//      anti-alias lattice -> biquad_2 -> line-out scale -> f32 / int32 codec frames
 //                                         audio_driver.c:2436-2592, 2832-2923
-//    The two waves form a 2-stage pipeline over 32-frame calls (wave 1 works on call k while
-//    wave 0 works on call k+1), halving the serial dependency chain per channel.  All state
-//    sits in registers for the whole launch; the AGC look-ahead ring sits in LDS.
+//    Small batches: a wave pipeline over 32-frame calls, one wave per stage (five roles: pre, agc,
+//    audio, aa, output; six with the AM / SAM demodulator), role s working on call it - s in step
+//    it, hand-offs through double-buffered LDS with one barrier per step, plus four tail waves
+//    that run the board's output stage and the stores.  All state sits in registers for the whole
+//    launch.  With the device hand-off the pipeline's ends are skewed across launches (BackSched),
+//    and one persistent launch can run call after call (PersistCtl).
+//    Large batches: rx_back_fused (every stage in one wave per 64 channels, no LDS hand-offs),
+//    rx_chain (front passes and fused back end in one kernel); rx_back_stereo, rx_notch and rx_fm
+//    for the stereo, auto-notch and FM plans.
 //
 // Arithmetic: exactly the reference's binary32 operation sequence (compiled with
 // -ffp-contract=off), so outputs are bit-identical to the firmware built for x86
@@ -779,9 +785,7 @@ __device__ __forceinline__ int to_dma(float f)
 
 // rx_back_fused: waves per SIMD the register allocation targets (2: 256 VGPRs, no scratch; 3
 // spills to scratch and measured 0.265 vs 0.217 ms at 1M x 64)
-#ifndef UHSDR_FUSED_WAVES
-#define UHSDR_FUSED_WAVES 2
-#endif
+constexpr int FUSED_WAVES = 2;
 
 // demodulator kinds of rx_back (DM): the SSB/CW/DIGI sum I +- Q happens in rx_front
 enum { DM_NONE = 0, DM_AM = 1, DM_SAM = 2, DM_SAM_SB = 3 /* SAM with the allpass sideband selector */,
@@ -909,9 +913,6 @@ struct InStage
     float xnext[NDC];
     const float* lds;
     bool gave_up = false;                                // DW: this launch's poll gave up
-#ifdef UHSDR_PDEBUG
-    unsigned arrived = 0;
-#endif
     int lim = -1;                                        // prefetch bound (sub-calls); -1: the launch's calls
 
     __device__ __forceinline__ void fetch(const BackArgs& a, const BackLane& l, int call)
@@ -935,13 +936,7 @@ struct InStage
             // read only after the pre role's peek found it published)
             if (call == 0) dflag_wait(a, a.dwait, a.dtarget, gave_up);
             // the persistent back end runs on into a granted call before its front has arrived
-            if (PERS && a.pctl && call == l.calls)
-            {
-                dflag_wait(a, a.dwait_next, a.dnext, gave_up);
-#ifdef UHSDR_PDEBUG
-                arrived = __hip_atomic_load(a.dwait_next + blockIdx.x * CNT_PITCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-            }
+            if (PERS && a.pctl && call == l.calls) dflag_wait(a, a.dwait_next, a.dnext, gave_up);
             const float* src = call < l.calls ? a.adec + (size_t)l.cl * a.Nd + call * NDC
                                               : a.adec_next + (size_t)l.cl * a.Nd + (call - l.calls) * NDC;
 #pragma unroll
@@ -976,9 +971,6 @@ struct InStage
 //      (IIR_AntiAlias, :2581-2590); state [S][C] in `st` ----
 // PK: the packed form (lattice_step_pk); the fused back end keeps the scalar one, where the
 // packed form's extra live pairs cost SGPR spills and scratch at no gain (it is not issue-bound)
-#ifndef UHSDR_FUSED_PK
-#define UHSDR_FUSED_PK false
-#endif
 template <int S, bool PK = true>
 struct LatticeStage
 {
@@ -1816,14 +1808,6 @@ extern "C" int uhsdr_trace_read(void* out)
 // covers exactly the launch's own n sub-calls.  A launch that finds the next call unpublished drains
 // as before and the next one fills.
 constexpr int BACK_SKEW = 4;            // back_roles(DM_NONE) - 1
-// BackSched's second chance at running ahead (rx_back_pre): 0 decides on the early peek alone
-#ifndef UHSDR_LATE_EXT
-#define UHSDR_LATE_EXT 1
-#endif
-// and its pre role's speculative first input of a skewed launch: 0 loads it after the skew word
-#ifndef UHSDR_SPEC_IN
-#define UHSDR_SPEC_IN 1
-#endif
 struct BackSched
 {
     int steps, gofs;
@@ -1869,19 +1853,6 @@ struct BackSched
         return s;
     }
 };
-#ifdef UHSDR_PDEBUG
-// (tools/debug_persist2.py) per call (seq % 64), group 0's pre role: seq, adec_next, cnt, target,
-// arrival count after the wait, dst from the descriptor, fast path, gave up
-__device__ unsigned long long g_pdbg[64][8];
-__device__ unsigned long long g_pdbg2[64][4][2];   // per call and group 0..3: decision word seen, polls
-__device__ unsigned long long g_ptime[1024][8];    // per call (seq % 1024): group 0 at g = 4 / n-4 / n-1 / after the decision / n-3 after the grant / n-2; group 1 before / after its decision
-extern "C" int uhsdr_pdbg_read(void* out)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pdbg), sizeof(g_pdbg)) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol((char*)out + sizeof(g_pdbg), HIP_SYMBOL(g_pdbg2), sizeof(g_pdbg2)) != hipSuccess) return -1;
-    return hipMemcpyFromSymbol((char*)out + sizeof(g_pdbg) + sizeof(g_pdbg2), HIP_SYMBOL(g_ptime), sizeof(g_ptime)) == hipSuccess ? 0 : -1;
-}
-#endif
 // the persistent back end (PersistCtl): its control words and descriptors live in host memory
 __device__ __forceinline__ unsigned sys_load(const unsigned* p)
 {
@@ -2028,8 +1999,8 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
     if (prep) ag.load(a, l, A);
     // a launch that starts skewed takes sub-call BACK_SKEW first: its input (found arrived by the
     // previous launch's peek, a kernel boundary ago) and ring slot are loaded before the skew word is
-    // consumed, so the role's entry waits one memory latency, not two (UHSDR_SPEC_IN)
-    const bool spec = UHSDR_SPEC_IN && DM == DM_NONE && a.skew && l.calls > BACK_SKEW;
+    // consumed, so the role's entry waits one memory latency, not two
+    const bool spec = DM == DM_NONE && a.skew && l.calls > BACK_SKEW;
     if (spec)
     {
         in.fetch(a, l, BACK_SKEW);
@@ -2111,9 +2082,6 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
                 v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(pdec(s1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             }
             go = (v >> 1) == want && !(v & 1u);
-#ifdef UHSDR_PDEBUG
-            if (blockIdx.x < 4 && l.lane == 0) { g_pdbg2[s1 % 64][blockIdx.x][0] = v; g_pdbg2[s1 % 64][blockIdx.x][1] = in.gave_up; }
-#endif
             if (go && !fast)
             {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // written before the grant group 0 saw
@@ -2127,14 +2095,6 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
             a.dwait_next = (const unsigned*)desc_u64(dw, DW_CNT);
             a.dnext = desc_u32(dw, DW_TARGET);
             if (l.lane < 16) lds.desc[(s1 & 1) * 16 + l.lane] = dw;   // the tail waves' copy
-#ifdef UHSDR_PDEBUG
-            if (blockIdx.x == 0 && l.lane == 0)
-            {
-                unsigned long long* r = g_pdbg[s1 % 64];
-                r[0] = s1; r[1] = (unsigned long long)a.adec_next; r[2] = (unsigned long long)a.dwait_next;
-                r[3] = a.dnext; r[5] = desc_u64(dw, DW_DST); r[6] = fast;
-            }
-#endif
         }
         glim = go ? l.calls + BACK_SKEW : l.calls;
         in.lim = go ? l.calls + BACK_SKEW + 1 : l.calls;  // + the next call's first sub-call of this role
@@ -2163,18 +2123,10 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
     BACK_ROLE_LOOP(DM ? 1 : 0)
         if (pers)
         {
-#ifdef UHSDR_PDEBUG
-            if (blockIdx.x == 0 && l.lane == 0)
-            {
-                if (call == 4) g_ptime[seq % 1024][0] = __builtin_amdgcn_s_memrealtime();
-                if (call == l.calls - 4) g_ptime[seq % 1024][1] = __builtin_amdgcn_s_memrealtime();
-                if (call == l.calls - 1) g_ptime[seq % 1024][2] = __builtin_amdgcn_s_memrealtime();
-            }
-#endif
             // after the launch's first call the control tail wave has read this call's grant and
             // descriptor from host memory during the previous call (rx_back_tail): LDS reads here. A
             // host-memory load of this wave's own would hold up its next HBM load's wait (one in-order
-            // vmcnt): 5-9 us per call measured (UHSDR_PDEBUG, tools/debug_persist3.py)
+            // vmcnt): 5-9 us per call measured with shader-clock stamps in this loop
             const bool have_ctl = seq != a.seq0;
             if (call == l.calls - 4 && !have_ctl) pctl_load();
             if (call == l.calls - 3)
@@ -2199,9 +2151,6 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
                         dw = desc_word_load(pdesc(seq + 1), l.lane);
                     }
                 }
-#ifdef UHSDR_PDEBUG
-                if (blockIdx.x == 0 && l.lane == 0) g_ptime[seq % 1024][4] = __builtin_amdgcn_s_memrealtime();
-#endif
                 // group 0: granted already -- published now, two steps before the others need it
                 if (leader && fast && pers_granted(a.pepoch, seq + 1, gw))
                 {
@@ -2210,15 +2159,7 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
                 }
             }
             if (call == l.calls - 2 && !leader) dv = __hip_atomic_load(pdec(seq + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef UHSDR_PDEBUG
-            if (call == l.calls - 2 && blockIdx.x == 0 && l.lane == 0) g_ptime[seq % 1024][5] = __builtin_amdgcn_s_memrealtime();
-            if (call == l.calls - 1 && blockIdx.x == 1 && l.lane == 0) g_ptime[seq % 1024][6] = __builtin_amdgcn_s_memrealtime();
-#endif
             if (call == l.calls - 1) pers_decide();
-#ifdef UHSDR_PDEBUG
-            if (call == l.calls - 1 && blockIdx.x == 1 && l.lane == 0) g_ptime[seq % 1024][7] = __builtin_amdgcn_s_memrealtime();
-            if (call == l.calls - 1 && blockIdx.x == 0 && l.lane == 0) g_ptime[seq % 1024][3] = __builtin_amdgcn_s_memrealtime();
-#endif
         }
         else if (sch.may_ext)
         {
@@ -2226,9 +2167,9 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
             if (call == l.calls - 1)
             {
                 decide();
-                // second chance (UHSDR_LATE_EXT): the next call had not arrived two steps ago -- peek
-                // again now and consume it at this step's end, where the step's work has hidden it
-                if (UHSDR_LATE_EXT && !ext) peek();
+                // second chance: the next call had not arrived two steps ago -- peek again now and
+                // consume it at this step's end, where the step's work has hidden it
+                if (!ext) peek();
             }
         }
         float xin[NDC];
@@ -2276,18 +2217,11 @@ __device__ __forceinline__ void rx_back_pre(const BackArgs& a0, BackLds lds)
 #pragma unroll
             for (int m = 0; m < NDC; ++m) po[m * BACK_CH] = s.step(xin[m], m);
         }
-        if (UHSDR_LATE_EXT && !pers && sch.may_ext && call == l.calls - 1 && !ext)
+        if (!pers && sch.may_ext && call == l.calls - 1 && !ext)
         {
             decide();                                  // the LDS word is read after this step's barrier
             if (ext) in.fetch(a, l, l.calls);          // g = n, consumed by in.begin at the next step
         }
-#ifdef UHSDR_PDEBUG
-        if (pers && call == l.calls - 1 && ext && blockIdx.x == 0 && l.lane == 0)
-        {
-            g_pdbg[(seq + 1) % 64][4] = __builtin_amdgcn_readfirstlane(in.arrived);
-            g_pdbg[(seq + 1) % 64][7] = in.gave_up;
-        }
-#endif
         if (pers)
         {
             // a give-up poisons the output from here on (the output role reads the word every sub-call)
@@ -2537,18 +2471,12 @@ __device__ __forceinline__ void rx_back_aa(const BackArgs& a, BackLds lds)
 }
 
 // (2 tail waves took 4500-5500 cycles per step with mcHF codec frames, above the anti-alias role)
-#ifndef UHSDR_BACK_TAILS
-#define UHSDR_BACK_TAILS 4
-#endif
-constexpr int BACK_TAILS = UHSDR_BACK_TAILS;
-// tail waves of a back end: BACK_TAILS for the demodulator-free pipeline; UHSDR_DM_TAILS for the AM /
-// SAM ones, 0 (the output role stores its call itself): their grids are large (C3: 512 workgroups)
+constexpr int BACK_TAILS = 4;
+// tail waves of a back end: BACK_TAILS for the demodulator-free pipeline; none for the AM / SAM
+// ones (the output role stores its call itself): their grids are large (C3: 512 workgroups)
 // and 4 more waves per workgroup took C3's SAM back end from 0.118 to 0.193 ms
 // (profiles/r06_configs_tails.jsonl)
-#ifndef UHSDR_DM_TAILS
-#define UHSDR_DM_TAILS 0
-#endif
-__host__ __device__ constexpr int back_tails(int dm) { return dm == DM_NONE ? BACK_TAILS : UHSDR_DM_TAILS; }
+__host__ __device__ constexpr int back_tails(int dm) { return dm == DM_NONE ? BACK_TAILS : 0; }
 template <int DM, bool PERS>
 __device__ __forceinline__ void rx_back_output(const BackArgs& a, BackLds lds)
 {
@@ -2691,12 +2619,9 @@ __global__ void __launch_bounds__((back_roles(DM) + back_tails(DM)) * BACK_CH) r
     __builtin_amdgcn_s_setprio(3);
     // readfirstlane makes the role provably wave-uniform (scalar branches)
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x / BACK_CH) - (DM ? 1 : 0);
-#ifndef UHSDR_ROLE_PRIO
-#define UHSDR_ROLE_PRIO 1
-#endif
     // AM / SAM: the demod role (the per-sample PLL recursion) is the pipeline's longest; the other
     // roles, sharing its SIMD, issue after it (still above a concurrent rx_front)
-    if (UHSDR_ROLE_PRIO && DM && role >= 0) __builtin_amdgcn_s_setprio(2);
+    if (DM && role >= 0) __builtin_amdgcn_s_setprio(2);
 #ifdef UHSDR_TRACE
     // (tools/trace_back.py) the wave's entry and exit in slot 39
     if ((threadIdx.x & (BACK_CH - 1)) == 0 && blockIdx.x < 64)
@@ -2755,10 +2680,10 @@ __device__ __forceinline__ void back_fused_body(const BackArgs& a, float* ys, in
     DemodStage<L, DM> dm;
     InStage<L, LDS_IN> in;
     in.lds = adl;
-    LatticeStage<PRE, UHSDR_FUSED_PK> pre;
+    LatticeStage<PRE, false> pre;
     AgcStage<L, W> ag;
     AudioStage<L, PH, DM> au;
-    LatticeStage<AA, UHSDR_FUSED_PK> aa;
+    LatticeStage<AA, false> aa;
     OutputStage ou;
     if (DM) { dm.load(a, l); dm.fetch(a, l, 0); }
     else in.fetch(a, l, 0);
@@ -2770,13 +2695,11 @@ __device__ __forceinline__ void back_fused_body(const BackArgs& a, float* ys, in
     ou.load(a, l);
     // coefficients of the per-sample recursions into VGPRs (full-rate VOP2, no SGPR spills:
     // v_readlane refills 699 -> 104 per kernel, 0.220 -> 0.211 ms at 1M x 64)
-#ifndef UHSDR_FUSED_SGPR_COEF
     if (PRE > 0) { to_vgpr(pre.k); to_vgpr(pre.v); }
     if (AA > 0) { to_vgpr(aa.k); to_vgpr(aa.v); }
     to_vgpr(ou.b2);
     ou.lo = to_vgpr(ou.lo);
     if (!B1S) to_vgpr(au.b1);
-#endif
     ag.agc_on = AGC_ON;
     if (DM != DM_NONE) ag.dc = true;
     else if (DC) ag.dc_sel = true;
@@ -2836,13 +2759,10 @@ __device__ __forceinline__ void back_fused_agc(const BackArgs& a, float* ys, int
 // no scratch, 3 waves per SIMD.
 // (the compiler's resource report: the 24 ksps bodies with a pre-filter lattice need 207-220
 // VGPRs at FORM 0 and spill to scratch at 3 waves, so they keep 2)
-#ifndef UHSDR_FUSED1_WAVES
-#define UHSDR_FUSED1_WAVES 3
-#endif
-__host__ __device__ constexpr int fused1_waves(int pre, int L) { return (L == 2 && pre > 0) ? 2 : UHSDR_FUSED1_WAVES; }
+__host__ __device__ constexpr int fused1_waves(int pre, int L) { return (L == 2 && pre > 0) ? 2 : 3; }
 template <int PRE, int AA, int L, int PH, int W, int DM, bool DC = true, int FORM = 0>
 __global__ void __launch_bounds__(BACK_CH)
-__attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_SAM_SB ? 1 : UHSDR_FUSED_WAVES))) rx_back_fused(BackArgs a)
+__attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_SAM_SB ? 1 : FUSED_WAVES))) rx_back_fused(BackArgs a)
 {
     __shared__ float ys[BACK_CH * FUSED_YPITCH];
     if constexpr (FORM == 1)
@@ -2867,7 +2787,7 @@ __attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_S
 // waves in different phases share a SIMD and its HBM stream.  The register budget is the back
 // end's (2 waves per SIMD); the front window and the back's output staging share one LDS region.
 template <int T1, int T2, int M, bool DF, int R, bool F, int PRE, int AA, int L, int PH, int W>
-__global__ void __launch_bounds__(FRONT_WAVE) __attribute__((amdgpu_waves_per_eu(UHSDR_FUSED_WAVES)))
+__global__ void __launch_bounds__(FRONT_WAVE) __attribute__((amdgpu_waves_per_eu(FUSED_WAVES)))
 rx_chain(FrontArgs fa, BackArgs ba, int front_floats)
 {
     static_assert(M == L, "decimation and interpolation rates agree");
@@ -3457,13 +3377,7 @@ constexpr int BACK_FUSED_MIN_CHANNELS = 131072;   // measured crossover (64-fram
 // launches (hipExtLaunchKernelGGL) a call costs the host 2 launches + 1 stream wait (+1 per
 // group) instead of 2 launches + 2 records + 2 waits: C2's host submission, 22-25 us per call,
 // was as long as the GPU's, and the GPU idled between calls (rocprofv3 kernel trace, r03).
-#ifndef UHSDR_PIPE_GROUP
-#define UHSDR_PIPE_GROUP 4
-#endif
-constexpr int PIPE_GROUP = UHSDR_PIPE_GROUP;
-#ifndef UHSDR_BACK_SKEW
-#define UHSDR_BACK_SKEW 1
-#endif
+constexpr int PIPE_GROUP = 4;
 constexpr int PIPE_BUFS = 2 * PIPE_GROUP;
 
 struct uhsdr_rx_s
@@ -3510,16 +3424,20 @@ struct uhsdr_rx_s
     long long calls_issued;  // process() calls
     long long pipe_calls;    // calls since the pipelined mode was entered (buffer index, group)
     int side_dirty;          // back-end work on the side stream not yet joined by a one-kernel call
-    // per-kernel timing (uhsdr_rx_enable_timing)
-    int timing;               // 0 off, else every timing-th call is bracketed
-    int tsample;              // the call being enqueued is a timed one
-    long long tcalls;         // calls since timing was enabled
-    int nev;
-    int nev_cap;
-    hipEvent_t* ev;          // [cap][NKERN kernels][start, stop]
-    uint8_t* evmask;         // [cap] kernels recorded in each timed call
-    float total_ms[4];
-    int launches[4];
+    // per-kernel timing (uhsdr_rx_enable_timing).  Written by uhsdr_rx_enable_timing (everything),
+    // rx_process (tsample, tcalls, nev, evmask), time_mark (evmask) and time_harvest (nev, the sums)
+    struct
+    {
+        int timing;               // 0 off, else every timing-th call is bracketed
+        int tsample;              // the call being enqueued is a timed one
+        long long tcalls;         // calls since timing was enabled
+        int nev;
+        int nev_cap;
+        hipEvent_t* ev;          // [cap][NKERN kernels][start, stop]
+        uint8_t* evmask;         // [cap] kernels recorded in each timed call
+        float total_ms[4];
+        int launches[4];
+    } tim;
     // failure contract of the bounded device-side polls: fail_host is host-mapped coherent memory
     // (fail_dev its device address) that a poll giving up sets to 1; process / join / synchronize
     // return UHSDR_TIMEOUT while it is set, uhsdr_rx_reset clears it
@@ -3527,27 +3445,38 @@ struct uhsdr_rx_s
     unsigned* fail_dev;
     unsigned spin_max;       // polls before a give-up (uhsdr_rx_set_handoff_bound; default 2^24)
     // pipelined device hand-off (uhsdr_rx_set_pipelined 2): rx_back polls the arrival counters the
-    // front waves of its group bump (FrontArgs::gcnt) instead of waiting on a cross-stream event
-    int dflag;
-    unsigned* gcnt;          // [PIPE_BUFS][groups][CNT_PITCH] arrival counters, one row per hand-off buffer
-    unsigned fills[PIPE_BUFS];   // counted front launches into each buffer since reset
-    int* skew;               // BackSched: per group, the wave pipeline ended a launch skewed (arena)
-    float* bnd;              // BackSched: the roles' pending input sub-calls (arena)
-    int dflag_grid;          // largest rx_back grid it is used for (half the CUs: the polling
-                             // workgroups never crowd out the front they wait for)
-    int back_attr;           // rx_back's LDS attribute raised for the reserved launch (1), failed (-1)
-    // persistent back end (uhsdr_rx_set_pipelined 3, PersistCtl): pmem = host-mapped coherent memory,
+    // front waves of its group bump (FrontArgs::gcnt) instead of waiting on a cross-stream event.
+    // Written by uhsdr_rx_create (gcnt, skew, bnd), uhsdr_rx_set_pipelined (dflag, dflag_grid),
+    // uhsdr_rx_reset and launch_fronts (fills) and back_launch_lds (back_attr)
+    struct
+    {
+        int dflag;
+        unsigned* gcnt;          // [PIPE_BUFS][groups][CNT_PITCH] arrival counters, one row per hand-off buffer
+        unsigned fills[PIPE_BUFS];   // counted front launches into each buffer since reset
+        int* skew;               // BackSched: per group, the wave pipeline ended a launch skewed (arena)
+        float* bnd;              // BackSched: the roles' pending input sub-calls (arena)
+        int dflag_grid;          // largest rx_back grid it is used for (half the CUs: the polling
+                                 // workgroups never crowd out the front they wait for)
+        int back_attr;           // rx_back's LDS attribute raised for the reserved launch (1), failed (-1)
+    } hand;
+    int pers;                // uhsdr_rx_set_pipelined 3: the persistent back end where a call admits it
+    // a run of the persistent back end (PersistCtl): pmem = host-mapped coherent memory,
     // PC_WORDS control words then DESC_RING call descriptors (pmem_dev: its device address); plive:
-    // a launch may still take the next grant; plast: the last call granted; pprev: the previous call
-    // ran on it (else the next one starts a new run: both streams synchronised, the words reset)
-    int pers;
-    unsigned* pmem;
-    unsigned* pmem_dev;
-    unsigned* pdec;          // device memory: group 0's decision per call (BackArgs::pdec)
-    int plive, pprev;
-    unsigned plast;
-    unsigned pepoch;         // the running (or last) launch's epoch (BackArgs::pepoch)
-    unsigned plaunches;      // persistent launches since creation (uhsdr_rx_debug_persist)
+    // a launch may still take the next grant; plast: the last call granted (a record only: no code
+    // reads it); pprev: the previous call ran on it (else the next one starts a new run: both
+    // streams synchronised, the words reset).
+    // Written by uhsdr_rx_set_pipelined (the memory; pprev), uhsdr_rx_reset (pprev), pers_begin
+    // (pprev, the words), pers_grant (plast, pepoch, plive, the words) and pers_close (plive): with
+    // sync_all, which calls it, the only way a run is closed
+    struct
+    {
+        unsigned* pmem;
+        unsigned* pmem_dev;
+        unsigned* pdec;          // device memory: group 0's decision per call (BackArgs::pdec)
+        int plive, pprev;
+        unsigned plast;
+        unsigned pepoch;         // the running (or last) launch's epoch (BackArgs::pepoch)
+    } run;
     int main_back;           // back-end state was last written on the handle's stream (a one-kernel
                              // schedule, a serial call, a reset): the next side-stream rx_back waits
                              // on ev_front, which orders it after that work; the device hand-off
@@ -3563,16 +3492,16 @@ static hipStream_t back_stream(const uhsdr_rx_s* h) { return side_mode(h) ? h->s
 
 static void time_mark(uhsdr_rx_s* h, int k, int which)
 {
-    if (!h->tsample) return;
-    (void)hipEventRecord(h->ev[((size_t)h->nev * NKERN + k) * 2 + which], k == K_BACK ? back_stream(h) : h->stream);
-    if (which) h->evmask[h->nev] |= (uint8_t)(1u << k);
+    if (!h->tim.tsample) return;
+    (void)hipEventRecord(h->tim.ev[((size_t)h->tim.nev * NKERN + k) * 2 + which], k == K_BACK ? back_stream(h) : h->stream);
+    if (which) h->tim.evmask[h->tim.nev] |= (uint8_t)(1u << k);
 }
 
 // the persistent back end's running launch gets no more grants (PersistCtl: the next call goes to a
 // new launch of the next epoch); it ends after the calls granted so far
 static void pers_close(uhsdr_rx_s* h)
 {
-    h->plive = 0;
+    h->run.plive = 0;
 }
 
 // every call enqueued so far, on both streams, has finished
@@ -3586,20 +3515,20 @@ static hipError_t sync_all(uhsdr_rx_s* h)
 
 static void time_harvest(uhsdr_rx_s* h)
 {
-    if (!h->nev) return;
+    if (!h->tim.nev) return;
     (void)sync_all(h);
-    for (int i = 0; i < h->nev; ++i)
+    for (int i = 0; i < h->tim.nev; ++i)
         for (int k = 0; k < NKERN; ++k)
         {
             float ms = 0.0f;
             const size_t e = ((size_t)i * NKERN + k) * 2;
-            if ((h->evmask[i] >> k & 1) && hipEventElapsedTime(&ms, h->ev[e], h->ev[e + 1]) == hipSuccess)
+            if ((h->tim.evmask[i] >> k & 1) && hipEventElapsedTime(&ms, h->tim.ev[e], h->tim.ev[e + 1]) == hipSuccess)
             {
-                h->total_ms[k] += ms;
-                h->launches[k] += 1;
+                h->tim.total_ms[k] += ms;
+                h->tim.launches[k] += 1;
             }
         }
-    h->nev = 0;
+    h->tim.nev = 0;
 }
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
@@ -3837,11 +3766,11 @@ extern "C" uhsdr_status uhsdr_rx_reset(uhsdr_rx_handle h)
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)h->tp, UHSDR_TWINPEAKS_WAIT, (size_t)h->C, h->stream));
     // the device hand-off's arrival counters restart with fills; a poll's give-up is cleared (the
     // state it poisoned was zeroed above)
-    HIPCHK(hipMemsetAsync(h->gcnt, 0, sizeof(unsigned) * CNT_PITCH * PIPE_BUFS * (((size_t)h->C + BACK_CH - 1) / BACK_CH), h->stream));
+    HIPCHK(hipMemsetAsync(h->hand.gcnt, 0, sizeof(unsigned) * CNT_PITCH * PIPE_BUFS * (((size_t)h->C + BACK_CH - 1) / BACK_CH), h->stream));
     *h->fail_host = 0;
-    memset(h->fills, 0, sizeof h->fills);
+    memset(h->hand.fills, 0, sizeof h->hand.fills);
     h->main_back = 1;
-    h->pprev = 0;
+    h->run.pprev = 0;
     if (h->bs.cw)
     {
         // old_siglevel starts at 0.001 (function static, cw_decoder.c:189)
@@ -3940,7 +3869,7 @@ extern "C" uhsdr_status uhsdr_rx_create(const uhsdr_rx_config* cfg, int32_t C, i
         hipMalloc((void**)&h->d_plan, sizeof(uhsdr_rx_plan)) != hipSuccess ||
         hipMalloc((void**)&h->d_taps2, sizeof(float) * 4 * TAPS2_MAX) != hipSuccess ||
         hipMalloc((void**)&h->d_lanemap, sizeof(uint16_t) * 4 * 64) != hipSuccess ||
-        hipMalloc((void**)&h->gcnt, sizeof(unsigned) * CNT_PITCH * PIPE_BUFS * (((size_t)C + BACK_CH - 1) / BACK_CH)) != hipSuccess ||
+        hipMalloc((void**)&h->hand.gcnt, sizeof(unsigned) * CNT_PITCH * PIPE_BUFS * (((size_t)C + BACK_CH - 1) / BACK_CH)) != hipSuccess ||
         hipHostMalloc((void**)&h->fail_host, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void**)&h->fail_dev, (void*)h->fail_host, 0) != hipSuccess)
     {
@@ -3957,8 +3886,8 @@ extern "C" uhsdr_status uhsdr_rx_create(const uhsdr_rx_config* cfg, int32_t C, i
     h->bs.interp = A + o_ip; h->bs.ring = A + o_ring; h->bs.agc = A + o_agc; h->bs.agci = (int*)(A + o_agci);
     h->bs.sam = am ? A + o_sam : nullptr;
     h->bs.cw = cw ? A + o_cw : nullptr;
-    h->skew = skewable ? (int*)(A + o_skew) : nullptr;
-    h->bnd = skewable ? A + o_bnd : nullptr;
+    h->hand.skew = skewable ? (int*)(A + o_skew) : nullptr;
+    h->hand.bnd = skewable ? A + o_bnd : nullptr;
     h->bs.notch = h->nv ? A + o_notch : nullptr;
     h->bs.ring1 = st ? A + o_ring1 : nullptr;
     h->bs.pre1 = st ? A + o_pre1 : nullptr; h->bs.aa1 = st ? A + o_aa1 : nullptr;
@@ -4159,9 +4088,9 @@ static BackArgs back_args(uhsdr_rx_s* h, float* adec, float* adec_q, float* audi
     ba.dwait_next = nullptr;
     ba.dnext = 0;
     ba.fcpw = 1;
-    ba.skew = h->skew;
-    ba.bnd = h->bnd;
-    ba.bnd_mid = h->bnd ? 6 * (BLK / h->plan.interp_L) : 0;   // (FM has no interpolator: interp_L 0)
+    ba.skew = h->hand.skew;
+    ba.bnd = h->hand.bnd;
+    ba.bnd_mid = h->hand.bnd ? 6 * (BLK / h->plan.interp_L) : 0;   // (FM has no interpolator: interp_L 0)
     ba.pctl = nullptr;
     ba.pdesc = nullptr;
     ba.pdec = nullptr;
@@ -4191,7 +4120,6 @@ static BackArgs back_args(uhsdr_rx_s* h, float* adec, float* adec_q, float* audi
     return ba;
 }
 
-
 // the failure word a bounded device-side poll sets when it gives up (BackArgs::fail)
 static uhsdr_status check_fail(const uhsdr_rx_s* h)
 {
@@ -4202,267 +4130,337 @@ static uhsdr_status check_fail(const uhsdr_rx_s* h)
     return UHSDR_TIMEOUT;
 }
 
+// ---- one call, step by step: rx_process below reads as the list of these steps ----
+
+#define RXSTEP(x) do { const uhsdr_status s_ = (x); if (s_ != UHSDR_OK) return s_; } while (0)
+
+// one kernel: front passes and back end per 64 channels, the hand-off in LDS
+static uhsdr_status chain_call(uhsdr_rx_s* h, const int32_t* iq, float* audio, float* audio0, int32_t* dst, bool fma)
+{
+    // after every back end still running on the pipelined mode's side stream (state it writes)
+    if (side_mode(h) && h->side_dirty)
+    {
+        HIPCHK(hipEventRecord(h->ev_join, h->side));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+        h->side_dirty = 0;
+    }
+    const FrontArgs fa = front_args(h, iq, 0, nullptr, nullptr);
+    const BackArgs ba = back_args(h, nullptr, nullptr, audio, audio0, dst);
+    time_mark(h, K_CHAIN, 0);
+    hipLaunchKernelGGL(fma ? h->cv->fn_fma : h->cv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(FRONT_WAVE),
+                       chain_lds(h), h->stream, fa, ba, (int)chain_front_floats(h));
+    HIPCHK(hipGetLastError());
+    time_mark(h, K_CHAIN, 1);
+    h->main_back = 1;
+    h->front_launches += 1;
+    return UHSDR_OK;
+}
+
+// Where a call of the two-kernel schedules goes: decided once, from the handle's state as the call
+// finds it, before anything is enqueued or stored.  Every later step reads the decision here.
+struct RxRoute
+{
+    long long pk;            // calls since the pipelined mode was entered
+    int par;                 // the call's hand-off buffer in the rotation (0: the handle's own)
+    int grp;                 // its group's completion event, ev_back[grp]
+    bool group_end;          // the group's last call: its rx_back records ev_back[grp]
+    float *adec, *adec_q;    // the call's hand-off buffers
+    int cpw;                 // the front's channels per wave
+    int bgroups;             // back-end workgroups (64-channel groups)
+    unsigned* gc;            // the buffer's arrival counters (device hand-off)
+    bool side;               // rx_back runs on the side stream
+    bool fused;              // a fused back end (one wave per group), not the wave pipeline
+    bool dfl;                // device hand-off
+    bool pm;                 // persistent back end
+    unsigned seq;            // the call's number in the persistent back end's protocol
+};
+
+static RxRoute route_call(const uhsdr_rx_s* h)
+{
+    RxRoute r;
+    // hand-off buffers of this call; pipelined: they rotate, in groups of PIPE_GROUP calls
+    r.pk = h->pipe_calls;
+    r.par = h->pipelined ? (int)(r.pk % PIPE_BUFS) : 0;
+    r.grp = (int)((r.pk / PIPE_GROUP) & 1);
+    r.group_end = h->pipelined && r.pk % PIPE_GROUP == PIPE_GROUP - 1;
+    r.adec = r.par ? h->adecp[r.par - 1] : h->adec;
+    r.adec_q = r.par ? h->adec_qp[r.par - 1] : h->adec_q;
+    r.cpw = FRONT_WAVE / (h->Nf / h->fv->R);
+    r.side = side_mode(h);
+    r.fused = h->schedule == UHSDR_SCHEDULE_SPLIT_FUSED || h->plan.stereo;
+    // device hand-off: rx_back (the wave pipeline, adec its only input from the front) polls
+    // the arrival counters its group's front waves bump (FrontArgs::gcnt) instead of waiting on
+    // ev_front: no barrier packet on the side stream, whose back ends then run back to back,
+    // and no signal kernel between the fronts (round 5's rx_handoff_signal: ~4.7 us of the
+    // handle stream per call)
+    r.bgroups = (h->C + BACK_CH - 1) / BACK_CH;
+    // (rx_fm measured slower with it: C4 FM 0.131-0.133 vs 0.115-0.117 ms, its 512 polling
+    // workgroups beside the fronts; profiles/r05_fm_handoff_ab.txt)
+    r.dfl = r.side && h->hand.dflag && !h->main_back && !r.fused && !h->nv && !h->fv->st &&
+            h->bv->dm == DM_NONE && r.bgroups <= h->hand.dflag_grid;
+    r.gc = h->hand.gcnt + (size_t)r.par * r.bgroups * CNT_PITCH;
+    // persistent back end (PersistCtl): the wave pipeline's skewed form, calls of 8+ sub-calls
+    r.pm = r.dfl && h->pers && h->hand.skew && h->N / BLK >= 2 * BACK_SKEW && !h->bs.cw &&
+           r.bgroups <= PC_MAX_GROUPS && h->bv->fn_pers;
+    r.seq = (unsigned)r.pk;
+    return r;
+}
+
+// the persistent back end's runs: a call that leaves one ends it, the first call of one starts it
+static uhsdr_status pers_begin(uhsdr_rx_s* h, const RxRoute& r)
+{
+    unsigned* const pw = h->run.pmem;
+    if (!r.pm && h->run.plive) HIPCHK(sync_all(h));   // leaving it: its launch ends, and everything completes
+    if (r.pm && !h->run.pprev)
+    {
+        // a new run: the buffers are free once everything enqueued has completed
+        HIPCHK(sync_all(h));
+        // no call's decision yet (ordered before the run's first launch on the side stream)
+        HIPCHK(hipMemsetAsync(h->run.pdec, 0xFF, sizeof(unsigned) * DESC_RING * PDEC_PITCH, h->side));
+        for (int g = 0; g < r.bgroups; ++g) __atomic_store_n(pw + PC_CONSUMED + g, r.seq, __ATOMIC_SEQ_CST);
+        __atomic_store_n(pw + PC_GRANT, 0u, __ATOMIC_SEQ_CST);
+        __atomic_store_n(pw + PC_EXIT, r.seq - 2, __ATOMIC_SEQ_CST);
+        __atomic_store_n(pw + PC_DECIDED, ((r.seq - 2) << 1) | 1u, __ATOMIC_SEQ_CST);
+    }
+    h->run.pprev = r.pm;
+    return UHSDR_OK;
+}
+
+// the host's waits on the persistent back end's control words: hot (no yield, so the word's change
+// is seen at once), bounded at 30 s (seconds at most are expected: a give-up still moves the words
+// on); what: the error's text, with a %u for the call
+template <class Pred>
+static uhsdr_status pers_spin(Pred done, const char* what, unsigned call)
+{
+    if (done()) return UHSDR_OK;                      // the usual case: no clock read
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;)
+    {
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30))
+        {
+            uhsdr_set_error(what, call);
+            return UHSDR_TIMEOUT;
+        }
+        if (done()) return UHSDR_OK;
+    }
+}
+
+// the call's hand-off buffer is free to refill
+static uhsdr_status wait_release(uhsdr_rx_s* h, const RxRoute& r)
+{
+    if (r.pm)
+    {
+        // the buffer (and descriptor) of call seq - PIPE_BUFS is refilled once the back end has
+        // read it: the host waits
+        const unsigned* pw = h->run.pmem;
+        const unsigned need = r.seq - (PIPE_BUFS - 1);
+        return pers_spin([&]() {
+            for (int g = 0; g < r.bgroups; ++g)
+                if ((int)(__atomic_load_n(pw + PC_CONSUMED + g, __ATOMIC_ACQUIRE) - need) < 0) return false;
+            return true;
+        }, "persistent back end: call %u's hand-off buffer not released within 30 s", r.seq);
+    }
+    // (Measured and dropped in round 6, profiles/r06_c2_ab_group.txt: skipping this wait when a
+    // host query finds the event complete, and groups of 8 or 16 calls: no gain at 20 steps,
+    // 0.0229-0.0235 vs 0.0221 ms at 1000 steps for the larger rotations)
+    // pipelined: at the start of a group, wait until the rx_back of the group two before it (the
+    // last readers of its buffers) is done
+    if (r.side && r.pk % PIPE_GROUP == 0) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_back[r.grp], 0));
+    return UHSDR_OK;
+}
+
+static uhsdr_status launch_fronts(uhsdr_rx_s* h, const RxRoute& r, const int32_t* iq, bool fma)
+{
+    const size_t lds = front_lds(h);
+    time_mark(h, K_FRONT, 0);
+    for (int f0 = 0; f0 < h->N; f0 += h->Nf)
+    {
+        FrontArgs fa = front_args(h, iq, f0, r.adec, r.adec_q);
+        if (r.dfl)
+        {
+            fa.gcnt = r.gc;
+            h->hand.fills[r.par] += 1;
+        }
+        const auto fn = fma ? h->fv->fn_fma : h->fv->fn;
+        const dim3 grid((h->C + r.cpw - 1) / r.cpw), block(FRONT_WAVE);
+        // pipelined: the call's last front launch records ev_front as it completes
+        if (r.side && !r.dfl && f0 + h->Nf >= h->N)
+            hipExtLaunchKernelGGL(fn, grid, block, lds, h->stream, nullptr, h->ev_front, 0, fa);
+        else
+            hipLaunchKernelGGL(fn, grid, block, lds, h->stream, fa);
+        HIPCHK(hipGetLastError());
+        h->front_launches += 1;
+    }
+    time_mark(h, K_FRONT, 1);
+    return UHSDR_OK;
+}
+
+// the device hand-off's fields of the back end's arguments (after the call's fronts: fills counts them)
+static void handoff_args(const uhsdr_rx_s* h, const RxRoute& r, BackArgs& bk)
+{
+    bk.dwait = r.gc;
+    bk.dtarget = h->hand.fills[r.par];
+    bk.fcpw = r.cpw;
+    // BackSched: run ahead into the next call if it has arrived by then.  The next buffer
+    // of the rotation is filled next by the next call only (its later reuse waits for this
+    // launch: ev_back), and its counters move only with a device hand-off front -- whose
+    // call's back end is then this same kernel on this stream (a mode change in between
+    // joins the side stream first, so no later front starts before this launch ends).  Not
+    // with the CW decoder (its per-call outputs belong to the launch's own call) or calls of
+    // fewer than BACK_SKEW 32-frame blocks.
+    if (h->hand.skew && h->N / BLK >= BACK_SKEW && !h->bs.cw)
+    {
+        const int parn = (int)((r.pk + 1) % PIPE_BUFS);
+        bk.adec_next = parn ? h->adecp[parn - 1] : h->adec;
+        bk.dwait_next = h->hand.gcnt + (size_t)parn * r.bgroups * CNT_PITCH;
+        bk.dnext = h->hand.fills[parn] + (unsigned)((h->N + h->Nf - 1) / h->Nf);
+    }
+}
+
+// the persistent back end's call: its descriptor, then its grant; a running launch takes it unless
+// it is closing after the previous call (PC_EXIT): then its decision tells (PersistCtl).  launch:
+// the call needs a launch of its own (none was running, or the running one closed), which bk is
+// then made the first call of
+static uhsdr_status pers_grant(uhsdr_rx_s* h, const RxRoute& r, BackArgs& bk, bool& launch)
+{
+    unsigned* const pw = h->run.pmem;
+    const unsigned seq = r.seq;
+    BackDesc* d = (BackDesc*)(pw + PC_WORDS) + seq % DESC_RING;
+    d->adec = r.adec;
+    d->cnt = r.gc;
+    d->audio = bk.audio;
+    d->audio0 = bk.audio0;
+    d->dst = bk.dst;
+    d->target = h->hand.fills[r.par];
+    d->beep_n0 = bk.beep_n0;
+    d->beep_n1 = bk.beep_n1;
+    d->beep_acc = bk.beep_acc;
+    __atomic_store_n(&d->seq, seq, __ATOMIC_RELEASE);
+    auto grant = [&]() { return h->run.pepoch << 24 | (seq & 0xFFFFFFu); };
+    launch = true;
+    if (h->run.plive)
+    {
+        __atomic_store_n(pw + PC_GRANT, grant(), __ATOMIC_SEQ_CST);
+        launch = false;
+        if (__atomic_load_n(pw + PC_EXIT, __ATOMIC_SEQ_CST) == seq - 1)
+        {
+            const unsigned want = (seq - 1) & 0x7FFFFFFFu;
+            unsigned dv = 0;
+            RXSTEP(pers_spin([&]() { return ((dv = __atomic_load_n(pw + PC_DECIDED, __ATOMIC_ACQUIRE)) >> 1) == want; },
+                             "persistent back end: no decision after call %u within 30 s", seq - 1));
+            launch = dv & 1u;                          // it closed: a new launch takes this call
+        }
+    }
+    h->run.plast = seq;
+    if (launch)
+    {
+        // a new launch, of the next epoch: grants of the old one's epoch no longer reach it
+        h->run.pepoch = (h->run.pepoch + 1) & 0xFFu;
+        __atomic_store_n(pw + PC_GRANT, grant(), __ATOMIC_SEQ_CST);
+        bk.pepoch = h->run.pepoch;
+        bk.pctl = h->run.pmem_dev;
+        bk.pdesc = (const BackDesc*)(h->run.pmem_dev + PC_WORDS);
+        bk.pdec = h->run.pdec;
+        bk.seq0 = seq;
+        bk.adec_next = nullptr;
+        bk.dwait_next = nullptr;
+        h->run.plive = 1;
+    }
+    return UHSDR_OK;
+}
+
+// dynamic LDS of the back-end launch (the fused kernels: none)
+static size_t back_launch_lds(uhsdr_rx_s* h, const RxRoute& r)
+{
+    if (r.fused) return 0;
+    // device hand-off: rx_back takes nearly all of a CU's LDS, so no rx_front workgroup of the
+    // next calls shares its SIMDs (the role waves are latency-bound; a front wave beside them
+    // stretches every step).  At most half the CUs (dflag_grid); C2 0.0263 -> 0.0257 ms at
+    // 1000 steps, 20 steps unchanged (profiles/r05_c2_back_reserve_ab.txt)
+    if (r.dfl)
+    {
+        if (!h->hand.back_attr)
+        {
+            h->hand.back_attr = hipFuncSetAttribute((const void*)h->bv->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                    (int)LDS_PER_CU) == hipSuccess ? 1 : -1;
+            if (h->hand.back_attr > 0 && h->bv->fn_pers &&
+                hipFuncSetAttribute((const void*)h->bv->fn_pers, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)LDS_PER_CU) != hipSuccess)
+                h->hand.back_attr = -1;
+            (void)hipGetLastError();
+        }
+        if (h->hand.back_attr > 0) return LDS_PER_CU - 4096;
+    }
+    return back_lds(h);
+}
+
+// the back end (after rx_notch, where the plan has one); launch: false when a running persistent
+// launch has taken the call (pers_grant)
+static uhsdr_status launch_back(uhsdr_rx_s* h, const RxRoute& r, const BackArgs& bk, bool launch)
+{
+    const hipStream_t bst = back_stream(h);
+    if (r.side && !r.dfl) HIPCHK(hipStreamWaitEvent(bst, h->ev_front, 0));
+    time_mark(h, K_BACK, 0);
+    if (h->nv)
+    {
+        hipLaunchKernelGGL(h->nv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(BACK_CH), 0, bst, bk);
+        HIPCHK(hipGetLastError());
+    }
+    const back_fn bfn = r.fused ? fused_back_fn(h) : r.pm ? h->bv->fn_pers : h->bv->fn;
+    // (the wave pipeline: its role waves and BACK_TAILS tail waves; rx_fm: its two; the fused kernels: one)
+    const int bwaves = r.fused ? 1 : h->bv->dm == DM_FM ? back_roles(DM_FM) : back_roles(h->bv->dm) + back_tails(h->bv->dm);
+    const dim3 bgrid((h->C + BACK_CH - 1) / BACK_CH), bblock(bwaves * BACK_CH);
+    const size_t blds = back_launch_lds(h, r);
+    // pipelined: the group's last rx_back records ev_back[grp] as it completes (the persistent
+    // back end: a launch only to start a run of calls; the buffers' reuse waits on PC_CONSUMED)
+    if (r.pm)
+    {
+        if (launch) hipLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, bk);
+    }
+    else if (r.side && r.group_end)
+        hipExtLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, nullptr, h->ev_back[r.grp], 0, bk);
+    else
+        hipLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, bk);
+    HIPCHK(hipGetLastError());
+    time_mark(h, K_BACK, 1);
+    return UHSDR_OK;
+}
+
 static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audio, float* audio0, int32_t* dst)
 {
     if (!h || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    {
-        const uhsdr_status fs = check_fail(h);
-        if (fs != UHSDR_OK) return fs;
-    }
-    if (h->timing && h->nev >= h->nev_cap) time_harvest(h);
-    h->tsample = h->timing && (h->tcalls++ % h->timing) == 0;
-    if (h->tsample) h->evmask[h->nev] = 0;
+    RXSTEP(check_fail(h));
+    if (h->tim.timing && h->tim.nev >= h->tim.nev_cap) time_harvest(h);
+    h->tim.tsample = h->tim.timing && (h->tim.tcalls++ % h->tim.timing) == 0;
+    if (h->tim.tsample) h->tim.evmask[h->tim.nev] = 0;
     const bool fma = h->precision == UHSDR_PRECISION_FMA;
     if (h->schedule == UHSDR_SCHEDULE_CHAIN)
-    {
-        // one kernel: front passes and back end per 64 channels, the hand-off in LDS
-        // after every back end still running on the pipelined mode's side stream (state it writes)
-        if (side_mode(h) && h->side_dirty)
-        {
-            HIPCHK(hipEventRecord(h->ev_join, h->side));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-            h->side_dirty = 0;
-        }
-        const FrontArgs fa = front_args(h, iq, 0, nullptr, nullptr);
-        const BackArgs ba = back_args(h, nullptr, nullptr, audio, audio0, dst);
-        time_mark(h, K_CHAIN, 0);
-        hipLaunchKernelGGL(fma ? h->cv->fn_fma : h->cv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(FRONT_WAVE),
-                           chain_lds(h), h->stream, fa, ba, (int)chain_front_floats(h));
-        HIPCHK(hipGetLastError());
-        time_mark(h, K_CHAIN, 1);
-        h->main_back = 1;
-        h->front_launches += 1;
-    }
+        RXSTEP(chain_call(h, iq, audio, audio0, dst, fma));
     else
     {
-        // hand-off buffers of this call; pipelined: rotate, and at the start of a group wait
-        // until the rx_back of the group two before it (the last readers of its buffers) is done
-        const long long pk = h->pipe_calls;
-        const int par = h->pipelined ? (int)(pk % PIPE_BUFS) : 0;
-        const int grp = (int)((pk / PIPE_GROUP) & 1);
-        const bool group_end = h->pipelined && pk % PIPE_GROUP == PIPE_GROUP - 1;
-        float* adec = par ? h->adecp[par - 1] : h->adec;
-        float* adec_q = par ? h->adec_qp[par - 1] : h->adec_q;
-        const int cpw = FRONT_WAVE / (h->Nf / h->fv->R);
-        const size_t lds = front_lds(h);
-        const bool side = side_mode(h);
-        const bool fused = h->schedule == UHSDR_SCHEDULE_SPLIT_FUSED || h->plan.stereo;
-        // device hand-off: rx_back (the wave pipeline, adec its only input from the front) polls
-        // the arrival counters its group's front waves bump (FrontArgs::gcnt) instead of waiting on
-        // ev_front: no barrier packet on the side stream, whose back ends then run back to back,
-        // and no signal kernel between the fronts (round 5's rx_handoff_signal: ~4.7 us of the
-        // handle stream per call)
-        const int bgroups = (h->C + BACK_CH - 1) / BACK_CH;
-        // (rx_fm measured slower with it: C4 FM 0.131-0.133 vs 0.115-0.117 ms, its 512 polling
-        // workgroups beside the fronts; profiles/r05_fm_handoff_ab.txt)
-        const bool dfl = side && h->dflag && !h->main_back && !fused && !h->nv && !h->fv->st &&
-                         h->bv->dm == DM_NONE && bgroups <= h->dflag_grid;
-        unsigned* const gc = h->gcnt + (size_t)par * bgroups * CNT_PITCH;
-        // persistent back end (PersistCtl): the wave pipeline's skewed form, calls of 8+ sub-calls
-        const bool pm = dfl && h->pers && h->skew && UHSDR_BACK_SKEW && h->N / BLK >= 2 * BACK_SKEW && !h->bs.cw &&
-                        bgroups <= PC_MAX_GROUPS && h->bv->fn_pers;
-        const unsigned seq = (unsigned)pk;
-        unsigned* const pw = h->pmem;
-        if (!pm && h->plive) HIPCHK(sync_all(h));     // leaving it: its launch ends, and everything completes
-        if (pm && !h->pprev)
-        {
-            // a new run: the buffers are free once everything enqueued has completed
-            HIPCHK(sync_all(h));
-            // no call's decision yet (ordered before the run's first launch on the side stream)
-            HIPCHK(hipMemsetAsync(h->pdec, 0xFF, sizeof(unsigned) * DESC_RING * PDEC_PITCH, h->side));
-            for (int g = 0; g < bgroups; ++g) __atomic_store_n(pw + PC_CONSUMED + g, seq, __ATOMIC_SEQ_CST);
-            __atomic_store_n(pw + PC_GRANT, 0u, __ATOMIC_SEQ_CST);
-            __atomic_store_n(pw + PC_EXIT, seq - 2, __ATOMIC_SEQ_CST);
-            __atomic_store_n(pw + PC_DECIDED, ((seq - 2) << 1) | 1u, __ATOMIC_SEQ_CST);
-        }
-        h->pprev = pm;
-        if (pm)
-        {
-            // the buffer (and descriptor) of call seq - PIPE_BUFS is refilled once the back end has
-            // read it: the host waits (seconds at most: a give-up still moves the word on)
-            const unsigned need = seq - (PIPE_BUFS - 1);
-            auto behind = [&]() {
-                for (int g = 0; g < bgroups; ++g)
-                    if ((int)(__atomic_load_n(pw + PC_CONSUMED + g, __ATOMIC_ACQUIRE) - need) < 0) return true;
-                return false;
-            };
-            if (behind())
-            {
-                const auto t0 = std::chrono::steady_clock::now();
-                while (behind())
-                {
-                    if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30))
-                    {
-                        uhsdr_set_error("persistent back end: call %u's hand-off buffer not released within 30 s", seq);
-                        return UHSDR_TIMEOUT;
-                    }
-                }
-            }
-        }
-        // (Measured and dropped in round 6, profiles/r06_c2_ab_group.txt: skipping this wait when a
-        // host query finds the event complete, and groups of 8 or 16 calls: no gain at 20 steps,
-        // 0.0229-0.0235 vs 0.0221 ms at 1000 steps for the larger rotations)
-        else if (side_mode(h) && pk % PIPE_GROUP == 0)
-            HIPCHK(hipStreamWaitEvent(h->stream, h->ev_back[grp], 0));
-        time_mark(h, K_FRONT, 0);
-        for (int f0 = 0; f0 < h->N; f0 += h->Nf)
-        {
-            FrontArgs fa = front_args(h, iq, f0, adec, adec_q);
-            if (dfl)
-            {
-                fa.gcnt = gc;
-                h->fills[par] += 1;
-            }
-            const auto fn = fma ? h->fv->fn_fma : h->fv->fn;
-            const dim3 grid((h->C + cpw - 1) / cpw), block(FRONT_WAVE);
-            // pipelined: the call's last front launch records ev_front as it completes
-            if (side && !dfl && f0 + h->Nf >= h->N)
-                hipExtLaunchKernelGGL(fn, grid, block, lds, h->stream, nullptr, h->ev_front, 0, fa);
-            else
-                hipLaunchKernelGGL(fn, grid, block, lds, h->stream, fa);
-            HIPCHK(hipGetLastError());
-            h->front_launches += 1;
-        }
-        time_mark(h, K_FRONT, 1);
-
+        const RxRoute r = route_call(h);
+        RXSTEP(pers_begin(h, r));
+        RXSTEP(wait_release(h, r));
+        RXSTEP(launch_fronts(h, r, iq, fma));
         // (the mcHF output stage runs inline in every back end: the wave pipeline's tail waves,
         // line_out4; round 5's finishing pass rx_line_out_mchf and its [C][N] scratch are gone)
-        BackArgs bk = back_args(h, adec, adec_q, audio, audio0, dst);
-        if (dfl)
-        {
-            bk.dwait = gc;
-            bk.dtarget = h->fills[par];
-            bk.fcpw = cpw;
-            // BackSched: run ahead into the next call if it has arrived by then.  The next buffer
-            // of the rotation is filled next by the next call only (its later reuse waits for this
-            // launch: ev_back), and its counters move only with a device hand-off front -- whose
-            // call's back end is then this same kernel on this stream (a mode change in between
-            // joins the side stream first, so no later front starts before this launch ends).  Not
-            // with the CW decoder (its per-call outputs belong to the launch's own call) or calls of
-            // fewer than BACK_SKEW 32-frame blocks.
-            if (UHSDR_BACK_SKEW && h->skew && h->N / BLK >= BACK_SKEW && !h->bs.cw)
-            {
-                const int parn = (int)((pk + 1) % PIPE_BUFS);
-                bk.adec_next = parn ? h->adecp[parn - 1] : h->adec;
-                bk.dwait_next = h->gcnt + (size_t)parn * bgroups * CNT_PITCH;
-                bk.dnext = h->fills[parn] + (unsigned)((h->N + h->Nf - 1) / h->Nf);
-            }
-        }
-        bool plaunch = true;
-        if (pm)
-        {
-            // the call's descriptor, then its grant; a running launch takes it unless it is closing
-            // after the previous call (PC_EXIT): then its decision tells (PersistCtl)
-            BackDesc* d = (BackDesc*)(pw + PC_WORDS) + seq % DESC_RING;
-            d->adec = adec;
-            d->cnt = gc;
-            d->audio = bk.audio;
-            d->audio0 = bk.audio0;
-            d->dst = bk.dst;
-            d->target = h->fills[par];
-            d->beep_n0 = bk.beep_n0;
-            d->beep_n1 = bk.beep_n1;
-            d->beep_acc = bk.beep_acc;
-            __atomic_store_n(&d->seq, seq, __ATOMIC_RELEASE);
-            auto grant = [&]() { return h->pepoch << 24 | (seq & 0xFFFFFFu); };
-            if (h->plive)
-            {
-                __atomic_store_n(pw + PC_GRANT, grant(), __ATOMIC_SEQ_CST);
-                plaunch = false;
-                if (__atomic_load_n(pw + PC_EXIT, __ATOMIC_SEQ_CST) == seq - 1)
-                {
-                    const unsigned want = (seq - 1) & 0x7FFFFFFFu;
-                    const auto t0 = std::chrono::steady_clock::now();
-                    unsigned dv;
-                    while (((dv = __atomic_load_n(pw + PC_DECIDED, __ATOMIC_ACQUIRE)) >> 1) != want)
-                    {
-                        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30))
-                        {
-                            uhsdr_set_error("persistent back end: no decision after call %u within 30 s", seq - 1);
-                            return UHSDR_TIMEOUT;
-                        }
-                    }
-                    plaunch = dv & 1u;               // it closed: a new launch takes this call
-                }
-            }
-            h->plast = seq;
-            if (plaunch)
-            {
-                // a new launch, of the next epoch: grants of the old one's epoch no longer reach it
-                h->pepoch = (h->pepoch + 1) & 0xFFu;
-                __atomic_store_n(pw + PC_GRANT, grant(), __ATOMIC_SEQ_CST);
-                bk.pepoch = h->pepoch;
-                bk.pctl = h->pmem_dev;
-                bk.pdesc = (const BackDesc*)(h->pmem_dev + PC_WORDS);
-                bk.pdec = h->pdec;
-                bk.seq0 = seq;
-                bk.adec_next = nullptr;
-                bk.dwait_next = nullptr;
-                h->plive = 1;
-                h->plaunches += 1;
-            }
-        }
-        const hipStream_t bst = back_stream(h);
-        if (side && !dfl) HIPCHK(hipStreamWaitEvent(bst, h->ev_front, 0));
-        time_mark(h, K_BACK, 0);
-        if (h->nv)
-        {
-            hipLaunchKernelGGL(h->nv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(BACK_CH), 0, bst, bk);
-            HIPCHK(hipGetLastError());
-        }
-        const back_fn bfn = fused ? fused_back_fn(h) : pm ? h->bv->fn_pers : h->bv->fn;
-        // (the wave pipeline: its role waves and BACK_TAILS tail waves; rx_fm: its two; the fused kernels: one)
-        const int bwaves = fused ? 1 : h->bv->dm == DM_FM ? back_roles(DM_FM) : back_roles(h->bv->dm) + back_tails(h->bv->dm);
-        const dim3 bgrid((h->C + BACK_CH - 1) / BACK_CH), bblock(bwaves * BACK_CH);
-#ifndef UHSDR_FUSED_LDS_PAD
-#define UHSDR_FUSED_LDS_PAD 0
-#endif
-#ifndef UHSDR_BACK_RESERVE
-#define UHSDR_BACK_RESERVE 1
-#endif
-        // (UHSDR_FUSED_LDS_PAD: unused dynamic LDS per fused workgroup, an occupancy cap for A/B)
-        size_t blds = fused ? (size_t)UHSDR_FUSED_LDS_PAD : back_lds(h);
-        // device hand-off: rx_back takes nearly all of a CU's LDS, so no rx_front workgroup of the
-        // next calls shares its SIMDs (the role waves are latency-bound; a front wave beside them
-        // stretches every step).  At most half the CUs (dflag_grid); C2 0.0263 -> 0.0257 ms at
-        // 1000 steps, 20 steps unchanged (profiles/r05_c2_back_reserve_ab.txt)
-        if (UHSDR_BACK_RESERVE && dfl)
-        {
-            if (!h->back_attr)
-            {
-                h->back_attr = hipFuncSetAttribute((const void*)h->bv->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)LDS_PER_CU) == hipSuccess ? 1 : -1;
-                if (h->back_attr > 0 && h->bv->fn_pers &&
-                    hipFuncSetAttribute((const void*)h->bv->fn_pers, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)LDS_PER_CU) != hipSuccess)
-                    h->back_attr = -1;
-                (void)hipGetLastError();
-            }
-            if (h->back_attr > 0) blds = LDS_PER_CU - 4096;
-        }
-        // pipelined: the group's last rx_back records ev_back[grp] as it completes (the persistent
-        // back end: a launch only to start a run of calls; the buffers' reuse waits on PC_CONSUMED)
-        if (pm)
-        {
-            if (plaunch) hipLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, bk);
-        }
-        else if (side && group_end)
-            hipExtLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, nullptr, h->ev_back[grp], 0, bk);
-        else
-            hipLaunchKernelGGL(bfn, bgrid, bblock, blds, bst, bk);
-        HIPCHK(hipGetLastError());
-        time_mark(h, K_BACK, 1);
+        BackArgs bk = back_args(h, r.adec, r.adec_q, audio, audio0, dst);
+        if (r.dfl) handoff_args(h, r, bk);
+        bool launch = true;
+        if (r.pm) RXSTEP(pers_grant(h, r, bk, launch));
+        RXSTEP(launch_back(h, r, bk, launch));
         if (h->pipelined) h->pipe_calls += 1;
-        if (side) h->side_dirty = 1;
-        h->main_back = !side;
+        if (r.side) h->side_dirty = 1;
+        h->main_back = !r.side;
     }
     h->calls_issued += 1;
-    if (h->tsample) h->nev++;
-    h->tsample = 0;
+    if (h->tim.tsample) h->tim.nev++;
+    h->tim.tsample = 0;
     h->dec_samples += h->Nd;
     h->calls_done += h->N / BLK;
     return UHSDR_OK;
 }
+#undef RXSTEP
 
 extern "C" uhsdr_status uhsdr_rx_process_host(uhsdr_rx_handle h, const int32_t* iq, float* audio, int32_t* dst)
 {
@@ -4565,20 +4563,6 @@ extern "C" uhsdr_status uhsdr_rx_set_front_block(uhsdr_rx_handle h, int32_t outp
     return UHSDR_OK;
 }
 
-// test hook: the persistent back end's control words (PC_GRANT, the epoch, PC_EXIT, PC_DECIDED,
-// PC_CONSUMED) and the host's plive / plast / plaunches
-extern "C" uhsdr_status uhsdr_rx_debug_persist(uhsdr_rx_handle h, uint32_t* out)
-{
-    if (!h || !out) return UHSDR_ARGUMENT_ERROR;
-    if (!h->pmem) return UHSDR_UNSUPPORTED;
-    const int w[5] = { PC_GRANT, -1, PC_EXIT, PC_DECIDED, PC_CONSUMED };
-    for (int i = 0; i < 5; ++i) out[i] = w[i] < 0 ? h->pepoch : __atomic_load_n(h->pmem + w[i], __ATOMIC_SEQ_CST);   // (group 0's PC_CONSUMED)
-    out[5] = (uint32_t)h->plive;
-    out[6] = h->plast;
-    out[7] = h->plaunches;
-    return UHSDR_OK;
-}
-
 extern "C" uhsdr_status uhsdr_rx_join(uhsdr_rx_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
@@ -4600,12 +4584,12 @@ extern "C" uhsdr_status uhsdr_rx_set_pipelined(uhsdr_rx_handle h, int32_t enable
                         "back end)", (int)enable);
         return UHSDR_ARGUMENT_ERROR;
     }
-    if (enable == 3 && !h->pmem)
+    if (enable == 3 && !h->run.pmem)
     {
-        HIPCHK(hipHostMalloc((void**)&h->pmem, PC_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(h->pmem, 0, PC_BYTES);
-        HIPCHK(hipHostGetDevicePointer((void**)&h->pmem_dev, h->pmem, 0));
-        HIPCHK(hipMalloc((void**)&h->pdec, sizeof(unsigned) * DESC_RING * PDEC_PITCH));
+        HIPCHK(hipHostMalloc((void**)&h->run.pmem, PC_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
+        memset(h->run.pmem, 0, PC_BYTES);
+        HIPCHK(hipHostGetDevicePointer((void**)&h->run.pmem_dev, h->run.pmem, 0));
+        HIPCHK(hipMalloc((void**)&h->run.pdec, sizeof(unsigned) * DESC_RING * PDEC_PITCH));
     }
     // into or out of the persistent back end: everything enqueued completes first
     if ((enable == 3) != (h->pers != 0)) HIPCHK(sync_all(h));
@@ -4623,7 +4607,7 @@ extern "C" uhsdr_status uhsdr_rx_set_pipelined(uhsdr_rx_handle h, int32_t enable
             if (h->adec_q) HIPCHK(hipMalloc((void**)&h->adec_qp[i], sizeof(float) * nd));
         }
     }
-    if (h->timing) time_harvest(h);
+    if (h->tim.timing) time_harvest(h);
     // leaving the mode: the side stream's work completes before the handle stream goes on
     if (!enable && h->pipelined)
     {
@@ -4640,14 +4624,14 @@ extern "C" uhsdr_status uhsdr_rx_set_pipelined(uhsdr_rx_handle h, int32_t enable
         h->pipe_calls = 0;
     }
     h->pipelined = enable != 0;
-    h->dflag = enable >= 2;
+    h->hand.dflag = enable >= 2;
     h->pers = enable == 3;
-    h->pprev = 0;
-    if (h->dflag && !h->dflag_grid)
+    h->run.pprev = 0;
+    if (h->hand.dflag && !h->hand.dflag_grid)
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-            h->dflag_grid = cus / 2;
+            h->hand.dflag_grid = cus / 2;
     }
     return UHSDR_OK;
 }
@@ -4687,19 +4671,19 @@ extern "C" int32_t uhsdr_rx_kernel_count(uhsdr_rx_handle h) { return h ? NKERN :
 extern "C" uhsdr_status uhsdr_rx_enable_timing(uhsdr_rx_handle h, int32_t enable)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (enable && !h->ev)
+    if (enable && !h->tim.ev)
     {
-        h->nev_cap = 1024;
-        h->ev = (hipEvent_t*)calloc((size_t)h->nev_cap * NKERN * 2, sizeof(hipEvent_t));
-        h->evmask = (uint8_t*)calloc((size_t)h->nev_cap, 1);
-        for (int i = 0; i < h->nev_cap * NKERN * 2; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
+        h->tim.nev_cap = 1024;
+        h->tim.ev = (hipEvent_t*)calloc((size_t)h->tim.nev_cap * NKERN * 2, sizeof(hipEvent_t));
+        h->tim.evmask = (uint8_t*)calloc((size_t)h->tim.nev_cap, 1);
+        for (int i = 0; i < h->tim.nev_cap * NKERN * 2; ++i) HIPCHK(hipEventCreate(&h->tim.ev[i]));
     }
-    if (h->timing) time_harvest(h);
-    h->timing = enable > 0 ? enable : 0;
-    h->tsample = 0;
-    h->tcalls = 0;
-    h->nev = 0;
-    for (int k = 0; k < NKERN; ++k) { h->total_ms[k] = 0.0f; h->launches[k] = 0; }
+    if (h->tim.timing) time_harvest(h);
+    h->tim.timing = enable > 0 ? enable : 0;
+    h->tim.tsample = 0;
+    h->tim.tcalls = 0;
+    h->tim.nev = 0;
+    for (int k = 0; k < NKERN; ++k) { h->tim.total_ms[k] = 0.0f; h->tim.launches[k] = 0; }
     return UHSDR_OK;
 }
 
@@ -4710,8 +4694,8 @@ extern "C" int32_t uhsdr_rx_kernel_times(uhsdr_rx_handle h, float* total_ms, int
     const int n = max_kernels < NKERN ? max_kernels : NKERN;
     for (int k = 0; k < n; ++k)
     {
-        if (total_ms) total_ms[k] = h->total_ms[k];
-        if (launches) launches[k] = h->launches[k];
+        if (total_ms) total_ms[k] = h->tim.total_ms[k];
+        if (launches) launches[k] = h->tim.launches[k];
     }
     return n;
 }
@@ -4734,11 +4718,11 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
             if (h->adec_qp[i]) (void)hipFree(h->adec_qp[i]);
         }
     }
-    if (h->ev)
+    if (h->tim.ev)
     {
-        for (int i = 0; i < h->nev_cap * NKERN * 2; ++i) (void)hipEventDestroy(h->ev[i]);
-        free(h->ev);
-        free(h->evmask);
+        for (int i = 0; i < h->tim.nev_cap * NKERN * 2; ++i) (void)hipEventDestroy(h->tim.ev[i]);
+        free(h->tim.ev);
+        free(h->tim.evmask);
     }
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->arena) (void)hipFree(h->arena);
@@ -4746,10 +4730,10 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
     if (h->d_plan) (void)hipFree(h->d_plan);
     if (h->d_taps2) (void)hipFree(h->d_taps2);
     if (h->d_lanemap) (void)hipFree(h->d_lanemap);
-    if (h->gcnt) (void)hipFree(h->gcnt);
+    if (h->hand.gcnt) (void)hipFree(h->hand.gcnt);
     if (h->fail_host) (void)hipHostFree((void*)h->fail_host);
-    if (h->pmem) (void)hipHostFree(h->pmem);
-    if (h->pdec) (void)hipFree(h->pdec);
+    if (h->run.pmem) (void)hipHostFree(h->run.pmem);
+    if (h->run.pdec) (void)hipFree(h->run.pdec);
     free(h);
     return UHSDR_OK;
 }
