@@ -354,7 +354,9 @@ uhsdr_status uhsdr_rx_join(uhsdr_rx_handle h);
  *   CHAIN       rx_chain: one kernel, each wave runs the front passes of its 64 channels and then
  *               their back end, the decimated hand-off kept in LDS (large batches).  SSB / CW /
  *               DIGI mono paths (no notch, no stereo, not AM / SAM / FM) with one front pass per
- *               call; elsewhere UHSDR_UNSUPPORTED.
+ *               call; elsewhere UHSDR_UNSUPPORTED.  Also refused: call sizes whose channels per
+ *               front wave, 64 / (frames_per_call / 8) rounded down, do not divide 64 -- 96-frame
+ *               (5) and 160-frame (3) calls; every power of two, 192 and 224 are taken.
  * Stereo, AM / SAM / FM and the LMS notch have their own back-end kernels and ignore SPLIT_*.
  * Returns UHSDR_UNSUPPORTED (handle unchanged) for a schedule the handle's path cannot run.
  * Takes effect from the next uhsdr_rx_process; get returns the resolved schedule. */
@@ -363,7 +365,14 @@ enum { UHSDR_SCHEDULE_AUTO = 0, UHSDR_SCHEDULE_SPLIT_PIPE = 1, UHSDR_SCHEDULE_SP
 uhsdr_status uhsdr_rx_set_schedule(uhsdr_rx_handle h, int32_t schedule);
 int32_t      uhsdr_rx_get_schedule(uhsdr_rx_handle h);    /* -1 for a null handle */
 /* FIR outputs per lane of the front passes: 8 (default: more waves per batch) or 16 (fewer LDS
-   window reads per MAC); UHSDR_UNSUPPORTED when the call size does not admit it.  Bit-identical. */
+   window reads per MAC); UHSDR_UNSUPPORTED when the call size does not admit it (the handle keeps
+   its block).  Bit-identical.  May be changed between calls in every mode of
+   uhsdr_rx_set_pipelined.  Once the handle has used the device hand-off or the persistent back
+   end (modes 2, 3), a change waits for every call enqueued so far, on both streams, and ends a
+   running persistent launch: the hand-off's arrival counters count front waves, whose number
+   changes with the block, so they restart.  In the serial mode and with the event hand-off it
+   costs no synchronisation.  A handle on the CHAIN schedule falls back to the split kernels when
+   rx_chain cannot run the new block. */
 uhsdr_status uhsdr_rx_set_front_block(uhsdr_rx_handle h, int32_t outputs_per_lane);
 
 /* ---- status side outputs: the RX chain's signals to the control plane ----

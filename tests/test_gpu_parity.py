@@ -19,7 +19,8 @@ from uhsdr_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def run_device(cfg, iq, frames_per_call, want_dst=True):
+def run_device(cfg, iq, frames_per_call, want_dst=True, hook=None):
+    """hook(chain, k) runs ahead of call k (k = 0: right after creation)"""
     import torch
     C, n, _ = iq.shape
     chain = U.RxChain(cfg, channels=C, frames=frames_per_call)
@@ -28,6 +29,8 @@ def run_device(cfg, iq, frames_per_call, want_dst=True):
     audio = torch.empty((C, frames_per_call), dtype=torch.float32, device="cuda")
     dst = torch.empty((C, frames_per_call, 2), dtype=torch.int32, device="cuda") if want_dst else None
     for off in range(0, n, frames_per_call):
+        if hook is not None:
+            hook(chain, off // frames_per_call)
         x = torch.from_numpy(np.ascontiguousarray(iq[:, off:off + frames_per_call])).cuda()
         chain.process(x, audio, dst)
         torch.cuda.synchronize()
@@ -233,8 +236,10 @@ def test_device_c2_batch_sampled_channels(cuda):
 
 @pytest.mark.parametrize("path", [48, 35, 55])
 def test_device_north_star_batch_sampled_channels(cuda, path):
-    """262144 channels x 64-frame calls (north-star regime, R = 16 front blocks): sampled
-    channels vs oracle, for each filter-path family."""
+    """262144 channels x 64-frame calls (north-star regime): sampled channels vs oracle, for each
+    filter-path family.  Only the narrow family (P35) runs 16 outputs per lane here (the library's
+    choice from 65536 channels on); P48 and P55 keep 8.  tests/test_gpu_front_shapes.py holds every
+    family at both block sizes."""
     import torch
     cfg = U.default_config(filter_path=path)
     C, n = 262144, 128

@@ -15,7 +15,8 @@ from uhsdr_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def run_pipelined(cfg, iq, N, toggle_at=None, join_each=False, switch=None, mode=1, modes=None, timeouts=None):
+def run_pipelined(cfg, iq, N, toggle_at=None, join_each=False, switch=None, mode=1, modes=None, timeouts=None,
+                  blocks=None):
     import torch
     C, n, _ = iq.shape
     calls = n // N
@@ -34,6 +35,8 @@ def run_pipelined(cfg, iq, N, toggle_at=None, join_each=False, switch=None, mode
             chain.set_schedule(switch[k])     # change kernel schedule between calls, still pipelined
         if modes is not None and k in modes:
             chain.set_pipelined(modes[k])     # hand-off kind (0 serial, 1 event, 2 device) between calls
+        if blocks is not None and k in blocks:
+            chain.set_front_block(blocks[k])  # front outputs per lane (8 / 16) between calls, no join
         chain.process(xs[k], audio[k], dst[k])
         if join_each:
             chain.join()

@@ -3691,11 +3691,15 @@ static uhsdr_status configure_front(uhsdr_rx_s* h, int R, bool strict)
     return st;
 }
 
-// can the handle run rx_chain: a chain instance, one front pass per call, LDS within a workgroup's
+// can the handle run rx_chain: a chain instance, one front pass per call, LDS within a workgroup's,
+// and front passes of cpw channels that tile the wave's 64 (rx_chain runs 64 / cpw of them and its
+// back end reads the LDS hand-off as lane == channel: with cpw = 3, 5, 6 or 10 -- 96- and 160-frame
+// calls, 320 at 16 outputs per lane -- the passes would cover fewer than 64 channels)
 static bool chain_ok(const uhsdr_rx_s* h)
 {
     // (the chain's back end has no DC removal: its paths are SSB / CW / DIGI, no notch)
-    return h->cv && h->fv->R == h->cv->R && h->Nf == h->N && chain_lds(h) <= 64 * 1024 && !h->plan.agc.remove_dc;
+    return h->cv && h->fv->R == h->cv->R && h->Nf == h->N && BACK_CH % (FRONT_WAVE / (h->Nf / h->fv->R)) == 0 &&
+           chain_lds(h) <= 64 * 1024 && !h->plan.agc.remove_dc;
 }
 
 static size_t back_lds(const uhsdr_rx_s* h);
@@ -4555,8 +4559,24 @@ extern "C" uhsdr_status uhsdr_rx_set_front_block(uhsdr_rx_handle h, int32_t outp
         uhsdr_set_error("front block %d: 8 or 16 outputs per lane", (int)outputs_per_lane);
         return UHSDR_ARGUMENT_ERROR;
     }
+    const int ocpw = FRONT_WAVE / (h->Nf / h->fv->R), oNf = h->Nf;
     const uhsdr_status st = configure_front(h, outputs_per_lane, true);
     if (st != UHSDR_OK) return st;
+    // The device hand-off counts front waves: its back ends wait for fills * (the front waves of
+    // their group), which holds only while every counted launch had the same channels per wave and
+    // frames per launch.  A block that changes either restarts the count, as uhsdr_rx_reset does:
+    // every call enqueued completes (a live persistent launch, which keeps its launch-time channels
+    // per wave, ends), then the arrival counters and fills go back to zero -- before any later back
+    // end can poll them.  A handle that never used the hand-off (fills all zero) pays nothing.
+    bool counted = false;
+    for (int i = 0; i < PIPE_BUFS; ++i) counted = counted || h->hand.fills[i] != 0;
+    if (counted && (FRONT_WAVE / (h->Nf / h->fv->R) != ocpw || h->Nf != oNf))
+    {
+        HIPCHK(sync_all(h));
+        HIPCHK(hipMemsetAsync(h->hand.gcnt, 0, sizeof(unsigned) * CNT_PITCH * PIPE_BUFS * (((size_t)h->C + BACK_CH - 1) / BACK_CH), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        memset(h->hand.fills, 0, sizeof h->hand.fills);
+    }
     // a CHAIN schedule needs the chain's block: fall back to the split kernels otherwise
     if (h->schedule == UHSDR_SCHEDULE_CHAIN && !chain_ok(h))
         h->schedule = h->bv->fused ? UHSDR_SCHEDULE_SPLIT_FUSED : UHSDR_SCHEDULE_SPLIT_PIPE;

@@ -193,7 +193,9 @@ class RxChain:
         return self.lib.uhsdr_rx_get_schedule(self.handle)
 
     def set_front_block(self, outputs_per_lane: int) -> None:
-        """FIR outputs per lane of the front passes, 8 or 16 (uhsdr_rx_set_front_block)."""
+        """FIR outputs per lane of the front passes, 8 or 16 (uhsdr_rx_set_front_block).  Allowed
+        between calls in every mode; once the device hand-off or the persistent back end has run
+        (set_pipelined 2, 3) a change synchronises both streams.  A refusal leaves the handle as it was."""
         _abi.check(self.lib.uhsdr_rx_set_front_block(self.handle, int(outputs_per_lane)), "uhsdr_rx_set_front_block")
 
     def join(self) -> None:
