@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UHSDR_ABI_VERSION 6
+#define UHSDR_ABI_VERSION 7
 
 typedef enum
 {
@@ -676,6 +676,46 @@ int32_t      uhsdr_sizeof_spectrum_plan(void);
 uhsdr_status uhsdr_rx_set_cw_outputs(uhsdr_rx_handle h, uint8_t* signal, float* energy);
 int32_t      uhsdr_rx_cw_blocks_max(uhsdr_rx_handle h);
 int32_t      uhsdr_rx_cw_blocks_last(uhsdr_rx_handle h);
+
+/* ---- CW decoder back end: Morse to text ----
+ * What CW_Decode_exe does after the mark/space decision of a block (drivers/audio/cw/cw_decoder.c:
+ * 326-375 and the decoder proper, :409-1078): the state-change ring, timing initialisation, data
+ * recognition, character identification, word-space and error correction, and the WPM estimate.
+ * One decoder per channel, every static of the firmware's starting at zero; results are exact to
+ * the reference.  blocksize 8..128 is cw_decoder_config.blocksize (samples at 12 ksps per block),
+ * spikecancel 0 off / 1 spike / 2 short, text_capacity >= 8; anything else UHSDR_ARGUMENT_ERROR.
+ * Outputs (owned by the handle; device pointers for a device handle, host pointers for a host one):
+ *   text  uint8 [C][text_capacity], a ring: character number k of a channel is at k % text_capacity,
+ *         exactly the bytes UiDriver_TextMsgPutChar receives (prosigns spelled out, '#', spaces)
+ *   total uint32 [C], characters emitted since reset
+ *   wpm   uint8 [C], cw_decoder_config.speed after the last block (0: not synchronised) */
+typedef struct uhsdr_cwdec_s* uhsdr_cwdec_handle;
+
+uhsdr_status uhsdr_cwdec_create(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity,
+                                void* stream, uhsdr_cwdec_handle* out);
+/* the same decoder with its state in host memory, for uhsdr_cwdec_process_host (no device call) */
+uhsdr_status uhsdr_cwdec_create_host(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity,
+                                     uhsdr_cwdec_handle* out);
+uhsdr_status uhsdr_cwdec_reset(uhsdr_cwdec_handle h);
+uhsdr_status uhsdr_cwdec_set_stream(uhsdr_cwdec_handle h, void* stream);
+/* state: uint8 [C][stride], one byte per CW block (ads.CW_signal, non-zero = mark), device memory;
+   decodes `blocks` <= stride blocks of every channel, stream-ordered */
+uhsdr_status uhsdr_cwdec_process(uhsdr_cwdec_handle h, const uint8_t* state, int32_t blocks, int32_t stride);
+/* the same step function on the CPU over host arrays, for a handle of uhsdr_cwdec_create_host */
+uhsdr_status uhsdr_cwdec_process_host(uhsdr_cwdec_handle h, const uint8_t* state, int32_t blocks, int32_t stride);
+uhsdr_status uhsdr_cwdec_outputs(uhsdr_cwdec_handle h, uint8_t** text, uint32_t** total, uint8_t** wpm);
+uhsdr_status uhsdr_cwdec_synchronize(uhsdr_cwdec_handle h);
+uhsdr_status uhsdr_cwdec_destroy(uhsdr_cwdec_handle h);
+/* CwGen_CharacterIdFunc (cw_gen.c:756): the character of a code of two bits per element (10 dot,
+   11 dash, first element highest); 0xfe for the empty code, 0xff when unknown */
+int32_t      uhsdr_cwdec_char_id(uint32_t code);
+
+/* Text decoding inside the RX chain: with enable != 0 the handle owns a decoder (blocksize from the
+   plan) and every uhsdr_rx_process decodes the CW blocks that call completed, after its back end.
+   Only for plan.cw_enabled with dmod_mode CW, where the firmware decodes (cw_decoder.c:355);
+   otherwise UHSDR_ARGUMENT_ERROR.  uhsdr_rx_reset resets the decoder.  Outputs as above. */
+uhsdr_status uhsdr_rx_set_cw_text(uhsdr_rx_handle h, int32_t enable, int32_t spikecancel, int32_t text_capacity);
+uhsdr_status uhsdr_rx_cw_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total, uint8_t** wpm);
 
 /* Key beep (AudioManagement_KeyBeep, audio_management.c:368-375 -> the softdds tone added to the
    output at audio_driver.c:2891-2898): the beep's DDS accumulator restarts at 0 and the tone

@@ -57,7 +57,7 @@ FRONT_BLOCK = 0     # --front-block: the RX lines' front outputs per lane (0 = t
 HANDOFF = "persistent"  # --handoff: the pipelined RX lines' front -> back hand-off (uhsdr_rx_set_pipelined 3 / 2 / 1)
 
 
-def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False):
+def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_text=False):
     import torch
     import bench
     import uhsdr_amd as U
@@ -72,6 +72,8 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False):
         sig = torch.empty((C, N // 32), dtype=torch.uint8, device="cuda")
         en = torch.empty((C, max(1, chain.cw_blocks_max)), dtype=torch.float32, device="cuda")
         chain.set_cw_outputs(sig, en)
+    if cw_text:
+        chain.set_cw_text(True, 0, 64)      # the Morse-to-text decoder on the blocks each call completes
     join = chain.join if pipelined else None
     ms = time_calls(lambda: chain.process(iq, audio, None), steps, warmup, join)
     chain.enable_timing(True)
@@ -80,12 +82,16 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False):
     chain.enable_timing(False)
     ab = bench.algorithmic_bytes(chain.plan, C, N, False)
     per = ab["chain"] / (C * N)
+    chars = int(chain.cw_text_outputs.read()[1].sum()) if cw_text else None
     out = {"workload": name, "channels": C, "frames_per_call": N, "pipelined": bool(pipelined), "ms_per_call": round(ms, 4),
            "msamples_per_s": round(C * N / ms / 1e3, 1),
            "kernel_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in kt.items()},
            "alg_bytes_per_frame": round(per, 2), "hbm_frac": round(C * N * per / ms / 1e6 / HBM_PEAK_GBS, 4),
            "finite": bool(torch.isfinite(audio).all().item()),
            "handoff_timeouts": chain.handoff_timeouts()}      # 0 required (include/uhsdr.h failure contract)
+    if cw_text:
+        out["cw_text"] = True
+        out["cw_text_chars"] = chars
     chain.close()
     if out["handoff_timeouts"]:
         raise RuntimeError(f"{name}: a device hand-off poll gave up: the line is invalid")
@@ -101,6 +107,8 @@ def main():
     ap.add_argument("--serial", action="store_true",
                     help="C4 FM-RX / SSB-TX handles in their serial mode (default: pipelined, measured faster there; "
                          "C3 SAM and C5 CW run serial, where the pipelined mode measured slower / the same)")
+    ap.add_argument("--cw-text", action="store_true",
+                    help="c5: after the usual line, the same leg again with the CW text decoder on (uhsdr_rx_set_cw_text)")
     ap.add_argument("--front-block", type=int, default=0, choices=[0, 8, 16], help="RX lines: front outputs per lane")
     ap.add_argument("--handoff", default="persistent", choices=["event", "device", "persistent"],
                     help="pipelined RX lines: the persistent back end (uhsdr_rx_set_pipelined 3; other back ends "
@@ -191,6 +199,9 @@ def main():
         cfg = U.default_config(filter_path=4, dmod_mode=U.DEMOD_CW)
         lines.append(rx_line("C5 per-GPU share: CW P4 (199-tap Hilbert @12k, 300 Hz lattice) + CW decoder Goertzel",
                              cfg, C, N, tiled(synth.cw_iq, C, N), a.steps, a.warmup, cw=True))
+        if a.cw_text:
+            lines.append(rx_line("C5 per-GPU share: CW P4 + CW decoder Goertzel + Morse-to-text (cw_decode)",
+                                 cfg, C, N, tiled(synth.cw_iq, C, N), a.steps, a.warmup, cw=True, cw_text=True))
     if "c5fir" in want:
         import numpy as np
         C, N = 1048576 // 8, 256

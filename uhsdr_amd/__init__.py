@@ -21,3 +21,4 @@ from .tx import TxChain  # noqa: F401
 from .spectrum import Spectrum  # noqa: F401
 from .i2s import Transceiver  # noqa: F401
 from .fir import FirBatch  # noqa: F401
+from .cwdec import CwDecoder  # noqa: F401

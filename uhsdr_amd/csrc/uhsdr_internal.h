@@ -69,6 +69,11 @@ extern const uhsdr_zoom_desc uhsdr_zoom_tables[5];
 
 int uhsdr_rx_mode_supported(const uhsdr_rx_plan* p);
 
+/* uhsdr_cwdec_process with the blocks spread over a row: block b of a channel is
+   state[c * stride + offset + b * step] (the RX chain's signal row, one byte per 32-frame call) */
+uhsdr_status uhsdr_cwdec_launch(uhsdr_cwdec_handle h, const uint8_t* state, int32_t blocks, int32_t stride,
+                                int32_t offset, int32_t step);
+
 /* thread-local last error text for uhsdr_last_error() */
 void uhsdr_set_error(const char* fmt, ...);
 

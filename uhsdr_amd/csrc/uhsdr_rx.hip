@@ -3412,6 +3412,8 @@ struct uhsdr_rx_s
     uint32_t beep_acc;       // its softdds accumulator at the next beep frame
     uint8_t* cw_signal;      // user outputs (uhsdr_rx_set_cw_outputs)
     float* cw_energy;
+    uhsdr_cwdec_handle cwt;  // Morse-to-text decoder (uhsdr_rx_set_cw_text), null when off
+    uint8_t* cwt_signal;     // its input [C][N/32] when the user set no signal buffer
     long long calls_done;
     long long front_launches; // oscillator ping-pong parity
     // pipelined mode (uhsdr_rx_set_pipelined): rx_back on a side stream, decimated hand-off
@@ -3784,6 +3786,13 @@ extern "C" uhsdr_status uhsdr_rx_reset(uhsdr_rx_handle h)
         HIPCHK(hipStreamSynchronize(h->stream));
         free(v);
     }
+    if (h->cwt)
+    {
+        const uhsdr_status cs = uhsdr_cwdec_set_stream(h->cwt, h->stream);
+        if (cs != UHSDR_OK) return cs;
+        const uhsdr_status cr = uhsdr_cwdec_reset(h->cwt);
+        if (cr != UHSDR_OK) return cr;
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->dec_samples = 0;
     h->calls_done = 0;
@@ -3960,6 +3969,58 @@ extern "C" uhsdr_status uhsdr_rx_set_cw_outputs(uhsdr_rx_handle h, uint8_t* sign
     return UHSDR_OK;
 }
 
+// Morse-to-text (uhsdr_cwdec.hip) on the blocks each call completes
+extern "C" uhsdr_status uhsdr_rx_set_cw_text(uhsdr_rx_handle h, int32_t enable, int32_t spikecancel, int32_t text_capacity)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    // the firmware decodes only in CW with the decoder on (cw_decoder.c:355)
+    if (!h->plan.cw_enabled || h->plan.dmod_mode != UHSDR_DEMOD_CW || !h->bs.cw)
+    {
+        uhsdr_set_error("cw text: needs the CW decoder front end (cw_decoder_enable) in demodulator mode CW, not mode %d",
+                        (int)h->plan.dmod_mode);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    uhsdr_cwdec_handle dec = nullptr;
+    uint8_t* sig = nullptr;
+    if (enable)
+    {
+        // (argument errors before anything changes)
+        const uhsdr_status st = uhsdr_cwdec_create(h->C, h->plan.cw_blocksize, spikecancel, text_capacity, h->stream, &dec);
+        if (st != UHSDR_OK) return st;
+        if (hipMalloc((void**)&sig, (size_t)h->C * (h->N / BLK)) != hipSuccess)
+        {
+            uhsdr_set_error("cw text: device allocation failed");
+            (void)uhsdr_cwdec_destroy(dec);
+            return UHSDR_DEVICE_ERROR;
+        }
+    }
+    HIPCHK(sync_all(h));
+    if (h->cwt) (void)uhsdr_cwdec_destroy(h->cwt);
+    if (h->cwt_signal) (void)hipFree(h->cwt_signal);
+    h->cwt = dec;
+    h->cwt_signal = sig;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_cw_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total, uint8_t** wpm)
+{
+    if (!h || !h->cwt) { uhsdr_set_error("cw text is off (uhsdr_rx_set_cw_text)"); return UHSDR_ARGUMENT_ERROR; }
+    return uhsdr_cwdec_outputs(h->cwt, text, total, wpm);
+}
+
+// the call's completed CW blocks through the text decoder, after the kernel that wrote the signal row
+// and on its stream.  cw0: CwDecode_RxProcessor's sample counter as the call found it; a block
+// completes at the 32-frame call that brings it to the block size, then every cpb calls
+static uhsdr_status launch_cw_text(uhsdr_rx_s* h, int cw0, hipStream_t st)
+{
+    if (!h->cwt || !h->cw_blocks_last) return UHSDR_OK;
+    const int ndc = BLK / h->plan.decimation_rate, bs = h->plan.cw_blocksize;
+    const int first = (bs - cw0 + ndc - 1) / ndc - 1, cpb = (bs + ndc - 1) / ndc;
+    const uhsdr_status ss = uhsdr_cwdec_set_stream(h->cwt, st);
+    if (ss != UHSDR_OK) return ss;
+    return uhsdr_cwdec_launch(h->cwt, h->cw_signal ? h->cw_signal : h->cwt_signal, h->cw_blocks_last, h->N / BLK, first, cpb);
+}
+
 extern "C" uhsdr_status uhsdr_rx_set_clip_output(uhsdr_rx_handle h, uint32_t* clip)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
@@ -4074,7 +4135,7 @@ static BackArgs back_args(uhsdr_rx_s* h, float* adec, float* adec_q, float* audi
     ba.s = h->bs;
     ba.C = h->C; ba.N = h->N; ba.Nd = h->Nd;
     ba.ring_phase = (int)(h->calls_done % (h->bv->dm == DM_FM ? 200 : AGC_Q));   // FM: fm_data.count phase
-    ba.cw_signal = h->bs.cw ? h->cw_signal : nullptr;
+    ba.cw_signal = h->bs.cw ? (h->cw_signal || !h->cwt ? h->cw_signal : h->cwt_signal) : nullptr;
     ba.cw_energy = h->bs.cw ? h->cw_energy : nullptr;
     ba.cw_count0 = h->cw_count;
     ba.cw_bmax = h->cw_bmax;
@@ -4438,8 +4499,12 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
     h->tim.tsample = h->tim.timing && (h->tim.tcalls++ % h->tim.timing) == 0;
     if (h->tim.tsample) h->tim.evmask[h->tim.nev] = 0;
     const bool fma = h->precision == UHSDR_PRECISION_FMA;
+    const int cw0 = h->cw_count;
     if (h->schedule == UHSDR_SCHEDULE_CHAIN)
+    {
         RXSTEP(chain_call(h, iq, audio, audio0, dst, fma));
+        RXSTEP(launch_cw_text(h, cw0, h->stream));
+    }
     else
     {
         const RxRoute r = route_call(h);
@@ -4453,6 +4518,7 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
         bool launch = true;
         if (r.pm) RXSTEP(pers_grant(h, r, bk, launch));
         RXSTEP(launch_back(h, r, bk, launch));
+        RXSTEP(launch_cw_text(h, cw0, back_stream(h)));
         if (h->pipelined) h->pipe_calls += 1;
         if (r.side) h->side_dirty = 1;
         h->main_back = !r.side;
@@ -4726,6 +4792,8 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
     (void)sync_all(h);
+    if (h->cwt) (void)uhsdr_cwdec_destroy(h->cwt);
+    if (h->cwt_signal) (void)hipFree(h->cwt_signal);
     if (h->side)
     {
         (void)hipEventDestroy(h->ev_front);

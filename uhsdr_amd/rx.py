@@ -48,6 +48,8 @@ class RxChain:
 
     def reset(self) -> None:
         _abi.check(self.lib.uhsdr_rx_reset(self.handle), "uhsdr_rx_reset")
+        if getattr(self, "_cw_text", None) is not None:
+            self._cw_text.seen[:] = 0
 
     def _shape_ok(self, t, last):
         shp = tuple(t.shape)
@@ -122,6 +124,31 @@ class RxChain:
         _abi.check(self.lib.uhsdr_rx_set_cw_outputs(self.handle, C.c_void_p(signal.data_ptr() if signal is not None else 0),
                                                     C.c_void_p(energy.data_ptr() if energy is not None else 0)),
                    "uhsdr_rx_set_cw_outputs")
+
+    def set_cw_text(self, enable: bool = True, spikecancel: int = 0, text_capacity: int = 64) -> None:
+        """Morse-to-text decoding of the CW blocks every following call completes
+        (uhsdr_rx_set_cw_text): only with the CW decoder front end on and dmod_mode CW."""
+        _abi.check(self.lib.uhsdr_rx_set_cw_text(self.handle, int(bool(enable)), int(spikecancel), int(text_capacity)),
+                   "uhsdr_rx_set_cw_text")
+        self._cw_text = None
+        if enable:
+            from .cwdec import TextOutputs
+            p = [C.c_void_p() for _ in range(3)]
+            _abi.check(self.lib.uhsdr_rx_cw_text_outputs(self.handle, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])),
+                       "uhsdr_rx_cw_text_outputs")
+            self._cw_text = TextOutputs(self.lib, self.channels, int(text_capacity), True, *(x.value for x in p))
+
+    def cw_text(self):
+        """Per channel, the bytes decoded since the last read (synchronises).  With .cw_text_outputs.read()
+        the text ring, the totals and the WPM estimate are available as arrays."""
+        if getattr(self, "_cw_text", None) is None:
+            raise RuntimeError("cw text is off: set_cw_text() first")
+        self.synchronize()
+        return self._cw_text.new_text()
+
+    @property
+    def cw_text_outputs(self):
+        return getattr(self, "_cw_text", None)
 
     @property
     def cw_blocks_max(self) -> int:

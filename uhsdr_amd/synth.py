@@ -234,3 +234,89 @@ def ssb_iq_torch(c0: int, nch: int, start: int, nframes: int, device, noise_sigm
     out[:, :, 0] = torch.clamp(torch.round(i_sig), -32768, 32767).to(torch.int32) * 65536
     out[:, :, 1] = torch.clamp(torch.round(q_sig), -32768, 32767).to(torch.int32) * 65536
     return out
+
+
+# International Morse code (ITU-R M.1677-1): letters, figures, punctuation
+MORSE = {
+    "A": ".-", "B": "-...", "C": "-.-.", "D": "-..", "E": ".", "F": "..-.", "G": "--.", "H": "....",
+    "I": "..", "J": ".---", "K": "-.-", "L": ".-..", "M": "--", "N": "-.", "O": "---", "P": ".--.",
+    "Q": "--.-", "R": ".-.", "S": "...", "T": "-", "U": "..-", "V": "...-", "W": ".--", "X": "-..-",
+    "Y": "-.--", "Z": "--..",
+    "1": ".----", "2": "..---", "3": "...--", "4": "....-", "5": ".....", "6": "-....", "7": "--...",
+    "8": "---..", "9": "----.", "0": "-----",
+    "=": "-...-", "/": "-..-.", "?": "..--..", '"': ".-..-.", ".": ".-.-.-", "@": ".--.-.", "'": ".----.",
+    "-": "-....-", ",": "--..--", ":": "---...",
+}
+
+
+def morse_keying(text: str):
+    """The message as (key down?, dot units) runs with PARIS timing: dot 1, dash 3, 1 between the
+    elements of a character, 3 between characters, 7 between words; ends with a word space.
+    ``<AR>`` sends the letters between the brackets run together (a prosign), ``<HH>`` the
+    eight-dot error sign."""
+    runs = []
+    i = 0
+    text = text.upper()
+    while i < len(text):
+        ch = text[i]
+        if ch == " ":
+            if runs:
+                runs[-1] = (False, 7)
+            i += 1
+            continue
+        if ch == "<":
+            j = text.index(">", i)
+            pattern = "".join(MORSE[c] for c in text[i + 1:j])
+            i = j + 1
+        else:
+            pattern = MORSE[ch]
+            i += 1
+        for el in pattern:
+            runs.append((True, 3 if el == "-" else 1))
+            runs.append((False, 1))
+        runs[-1] = (False, 3)
+    if runs:
+        runs[-1] = (False, 7)
+    return runs
+
+
+def morse_envelope(text: str, wpm: float, rate: float) -> np.ndarray:
+    """0/1 key state per sample at `rate` samples per second; a dot lasts 1.2 / wpm seconds."""
+    unit = 1.2 / wpm * rate
+    edges = np.rint(np.cumsum([0.0] + [u * unit for _, u in morse_keying(text)])).astype(np.int64)
+    env = np.zeros(int(edges[-1]), dtype=np.uint8)
+    for (down, _), a, b in zip(morse_keying(text), edges[:-1], edges[1:]):
+        if down:
+            env[a:b] = 1
+    return env
+
+
+def cw_text_iq(channels, start: int, nframes: int, text: str, wpm: float = 20.0, noise_sigma: float = 30.0,
+               carrier: float = 12000.0, tone: float = 750.0, amplitude: float = 1500.0, lead: int = 24000):
+    """A carrier at `carrier` + `tone` Hz (the receiver's sidetone pitch) keyed with `text` in
+    Morse code at `wpm` words per minute, repeated for ever, after `lead` frames of silence plus
+    a per-channel delay of up to one second; plus noise.  The CW text decoder's input."""
+    channels = np.asarray(channels, dtype=np.int64)
+    ch = channels.astype(np.uint64)
+    base = (np.uint64(SEED_BASE) + ch) << np.uint64(20)
+    delay = lead + np.floor(FS * _uniform(base + np.uint64(13))).astype(np.int64)
+    ph_c = 2.0 * np.pi * _uniform(base + np.uint64(12))
+    env = morse_envelope(text, wpm, FS)
+    reps = nframes // len(env) + 2
+    # cos / sin of the common phase once, turned by each channel's start phase
+    ph = 2.0 * np.pi * (carrier + tone) / FS * np.arange(start, start + nframes, dtype=np.float64)
+    c0, s0 = amplitude * np.cos(ph), amplitude * np.sin(ph)
+    i_sig = np.zeros((len(channels), nframes))
+    q_sig = np.zeros((len(channels), nframes))
+    for k in range(len(channels)):
+        first = max(int(delay[k]) - start, 0)          # frames of this call before the channel's keying starts
+        if first >= nframes:
+            continue
+        key = np.tile(env, reps)[(start + first - int(delay[k])) % len(env):][:nframes - first] != 0
+        cc, sc = np.cos(ph_c[k]), np.sin(ph_c[k])
+        i_sig[k, first:] = np.where(key, c0[first:] * cc - s0[first:] * sc, 0.0)
+        q_sig[k, first:] = np.where(key, s0[first:] * cc + c0[first:] * sc, 0.0)
+    if noise_sigma > 0:
+        ni, nq = _noise(channels, start, nframes, noise_sigma)
+        i_sig, q_sig = i_sig + ni, q_sig + nq
+    return _frames(i_sig, q_sig)
