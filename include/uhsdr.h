@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UHSDR_ABI_VERSION 7
+#define UHSDR_ABI_VERSION 8
 
 typedef enum
 {
@@ -716,6 +716,57 @@ int32_t      uhsdr_cwdec_char_id(uint32_t code);
    otherwise UHSDR_ARGUMENT_ERROR.  uhsdr_rx_reset resets the decoder.  Outputs as above. */
 uhsdr_status uhsdr_rx_set_cw_text(uhsdr_rx_handle h, int32_t enable, int32_t spikecancel, int32_t text_capacity);
 uhsdr_status uhsdr_rx_cw_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total, uint8_t** wpm);
+
+/* ---- RTTY decoder: Baudot to text, one decoder per channel ----
+ * What the firmware runs on every 12 ksps sample in DEMOD_DIGI with digital_mode RTTY
+ * (Rtty_Demodulator_ProcessSample, drivers/audio/rtty.c): mark and space band-passes, the
+ * automatic threshold correction (or the plain difference with atc_disable), the low-pass, the bit
+ * DPLL, the start-bit search, Baudot framing and the letters / figures tables.  Exact to the
+ * reference: the same bytes at the same samples.
+ *   shift_idx    0 .. 5: 85, 170, 200, 425, 450, 850 Hz (mark 915 Hz, space 915 Hz + shift)
+ *   speed_idx    0 .. 1: 45.45 and 50 baud (264 and 240 samples per bit)
+ *   stopbits_idx 0 .. 2: 1, 1.5 and 2 stop bits
+ *   text_capacity >= 8
+ * Outputs (device memory, or host memory for a host handle), valid once the work enqueued is complete:
+ *   text  uint8 [C][text_capacity], a ring: character k of a channel is at k % text_capacity;
+ *         exactly the bytes UiDriver_TextMsgPutChar receives, '\0', '\a', '\r' and '\n' included
+ *         (LTRS and FIGS only switch the table)
+ *   total uint32 [C], characters emitted since reset
+ * Not built: the RTTY modulator (Rtty_Modulator_GenSample), PSK, and text decoding of either kind
+ * in the uhsdr_i2s_* stream. */
+typedef struct uhsdr_rtty_s* uhsdr_rtty_handle;
+
+uhsdr_status uhsdr_rtty_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                               int32_t atc_disable, int32_t text_capacity, void* stream, uhsdr_rtty_handle* out);
+/* the same decoder with its state in host memory, for uhsdr_rtty_process_host (no device call) */
+uhsdr_status uhsdr_rtty_create_host(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                                    int32_t atc_disable, int32_t text_capacity, uhsdr_rtty_handle* out);
+uhsdr_status uhsdr_rtty_reset(uhsdr_rtty_handle h);
+uhsdr_status uhsdr_rtty_set_stream(uhsdr_rtty_handle h, void* stream);
+/* samples: f32 [C][stride], 12 ksps, device memory; decodes n <= stride samples of every channel,
+   stream-ordered */
+uhsdr_status uhsdr_rtty_process(uhsdr_rtty_handle h, const float* samples, int32_t n, int32_t stride);
+/* the same step function on the CPU over host arrays, for a handle of uhsdr_rtty_create_host */
+uhsdr_status uhsdr_rtty_process_host(uhsdr_rtty_handle h, const float* samples, int32_t n, int32_t stride);
+uhsdr_status uhsdr_rtty_outputs(uhsdr_rtty_handle h, uint8_t** text, uint32_t** total);
+uhsdr_status uhsdr_rtty_synchronize(uhsdr_rtty_handle h);
+uhsdr_status uhsdr_rtty_destroy(uhsdr_rtty_handle h);
+
+/* Digital-mode tap of the RX chain: tap = device f32 [C][N/4], written by every following
+   uhsdr_rx_process with a_buffer[0] after biquad_1, the sample the firmware hands its modems
+   (audio_driver.c:2537-2557); null turns it off.  Available where the firmware runs them: a 12 ksps
+   path of the SSB / CW / DIGI back-end family (mono), in every schedule; anything else gives
+   UHSDR_ARGUMENT_ERROR.  Launches with a tap run kernel instances of their own; with the tap on,
+   pipelined mode 3 (the persistent back end) runs as mode 2, as it does with the CW front end. */
+uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap);
+/* RTTY text inside the RX chain: with enable != 0 the handle owns a decoder (arguments as
+   uhsdr_rtty_create) and a tap row, unless the caller set one, and every uhsdr_rx_process decodes the
+   call's N/4 samples after the kernel that wrote them, on its stream.  Only for dmod_mode
+   UHSDR_DEMOD_DIGI on a path that has the tap; otherwise UHSDR_ARGUMENT_ERROR.  uhsdr_rx_reset
+   resets the decoder.  Outputs as uhsdr_rtty_outputs. */
+uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx,
+                                    int32_t stopbits_idx, int32_t atc_disable, int32_t text_capacity);
+uhsdr_status uhsdr_rx_rtty_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total);
 
 /* Key beep (AudioManagement_KeyBeep, audio_management.c:368-375 -> the softdds tone added to the
    output at audio_driver.c:2891-2898): the beep's DDS accumulator restarts at 0 and the tone

@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""Throughput of the stand-alone RTTY decoder (uhsdr_rtty_process, kernel rtty_decode) on FSK
+input: the 170 Hz / 45.45 baud / 1.5 stop bit fixture streams (tests/golden/rtty_*.npz, ATC on)
+tiled over the channels, a different case on neighbouring lanes, fed in calls of --samples
+12 ksps samples.
+
+    python tools/bench_rtty.py [--channels 65536] [--samples 512] [--calls 40]
+
+Prints one JSON line: ms per call and channel-samples per second, timed with device events over
+the calls after one warm-up pass, plus the host decoder's rate on one thread for scale."""
+import argparse
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--channels", type=int, default=65536)
+    ap.add_argument("--samples", type=int, default=512)
+    ap.add_argument("--calls", type=int, default=40)
+    a = ap.parse_args()
+    import torch
+    from uhsdr_amd import rtty, synth
+    config = (rtty.SHIFT_170, rtty.SPEED_45, rtty.STOP_1_5, 0)
+    files = sorted(f for f in glob.glob(os.path.join(ROOT, "tests", "golden", "rtty_*.npz")) if "rtty_chain_" not in f)
+    cases = [g["audio"] for g in map(synth.rtty_fixture, files) if g["config"] == config]
+    need = a.samples * a.calls
+    rows = np.stack([np.resize(s, need) for s in cases])
+    C = a.channels
+    pieces = []
+    for k in range(a.calls):
+        p = torch.from_numpy(np.ascontiguousarray(rows[:, k * a.samples:(k + 1) * a.samples])).cuda()
+        pieces.append(p.repeat((C + len(rows) - 1) // len(rows), 1)[:C].contiguous())
+    s = torch.cuda.current_stream()
+    dec = rtty.RttyDecoder(C, *config, capacity=64, stream=s.cuda_stream)
+    ms = []
+    for rep in range(2):                       # pass 0 warms up
+        dec.reset()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for p in pieces:
+            dec.process(p)
+        e1.record(s)
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / a.calls)
+    chars = int(dec.read()[1].astype(np.int64).sum())
+    host = rtty.RttyDecoder(len(rows), *config, capacity=64, host=True)
+    t0 = time.perf_counter()
+    host.process(np.ascontiguousarray(rows))
+    host_ns = (time.perf_counter() - t0) * 1e9 / rows.size
+    print(json.dumps({"workload": "rtty_decode: Baudot-to-text, fixture streams tiled over the lanes", "channels": C,
+                      "samples_per_call": a.samples, "calls": a.calls, "ms_per_call": round(ms[1], 4),
+                      "channel_samples_per_s": round(C * a.samples / (ms[1] * 1e-3), 0),
+                      "ns_per_channel_sample": round(ms[1] * 1e6 / (C * a.samples), 5),
+                      "characters": chars, "host_ns_per_channel_sample_1_thread": round(host_ns, 1)}))
+
+
+if __name__ == "__main__":
+    main()

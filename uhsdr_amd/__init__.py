@@ -22,3 +22,4 @@ from .spectrum import Spectrum  # noqa: F401
 from .i2s import Transceiver  # noqa: F401
 from .fir import FirBatch  # noqa: F401
 from .cwdec import CwDecoder  # noqa: F401
+from .rtty import RttyDecoder  # noqa: F401

@@ -707,6 +707,9 @@ struct BackArgs
     unsigned* pdec;
     unsigned seq0;
     unsigned pepoch;     // this launch's epoch: PC_GRANT's top byte while the host grants it calls
+    // digital-mode tap (uhsdr_rx_set_digi_tap): [C][Nd] a_buffer[0] after biquad_1, the sample the
+    // firmware hands its modems (audio_driver.c:2537-2557); read only by the TAP kernel instances
+    float* tap;
 };
 
 // Persistent back end (uhsdr_rx_set_pipelined 3).  One rx_back launch runs call after call with its
@@ -2346,7 +2349,7 @@ __device__ __forceinline__ void rx_back_agc(const BackArgs& a0, BackLds lds)
     }
 }
 
-template <int L, int PH, int W, int DM, bool PERS>
+template <int L, int PH, int W, int DM, bool PERS, bool TAP = false>
 __device__ __forceinline__ void rx_back_audio(const BackArgs& a, BackLds lds)
 {
     const BackLane l(a);
@@ -2403,7 +2406,14 @@ __device__ __forceinline__ void rx_back_audio(const BackArgs& a, BackLds lds)
         for (int m = 0; m < NDC; ++m)
         {
             float u[L];
-            s.step(x[m], u);
+            if constexpr (TAP)
+            {
+                const float t = s.step_dec(x[m]);
+                if (l.live && call < l.calls) a.tap[(size_t)l.c * a.Nd + call * NDC + m] = t;
+                s.interp(t, u);
+            }
+            else
+                s.step(x[m], u);
 #pragma unroll
             for (int j = 0; j < L; ++j) mo[(m * L + j) * BACK_CH] = u[j];
         }
@@ -2608,7 +2618,8 @@ __device__ __forceinline__ void rx_back_tail(const BackArgs& a0, BackLds lds, in
 
 // PRE / AA lattice stages, L interpolation factor, PH polyphase length, W AGC window,
 // DM demodulator (DM_NONE: SSB/CW/DIGI)
-template <int PRE, int AA, int L, int PH, int W, int DM, bool PERS = false>
+// TAP: the audio role also writes BackArgs::tap (an instance of its own; 12 ksps, DM_NONE)
+template <int PRE, int AA, int L, int PH, int W, int DM, bool PERS = false, bool TAP = false>
 __global__ void __launch_bounds__((back_roles(DM) + back_tails(DM)) * BACK_CH) rx_back(BackArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2637,7 +2648,7 @@ __global__ void __launch_bounds__((back_roles(DM) + back_tails(DM)) * BACK_CH) r
     else if (role == 1)
         rx_back_agc<L, W, DM, PERS>(a, lds);
     else if (role == 2)
-        rx_back_audio<L, PH, W, DM, PERS>(a, lds);
+        rx_back_audio<L, PH, W, DM, PERS, TAP>(a, lds);
     else if (role == 3)
         rx_back_aa<AA, DM, PERS>(a, lds);
     else if (role == 4)
@@ -2667,8 +2678,9 @@ __global__ void __launch_bounds__((back_roles(DM) + back_tails(DM)) * BACK_CH) r
 // time for the demodulating bodies, a select behind rx_notch)
 // LDS_IN (rx_chain): channel group grp, input from the wave's LDS hand-off adl
 // B1S: biquad_1's taps stay in SGPRs (it runs once per decimated sample; 20 VGPRs freed)
+// TAP: the decimated sample after biquad_1 also goes to BackArgs::tap (instances of their own)
 template <int PRE, int AA, int L, int PH, int W, int DM, bool AGC_ON, bool CW, bool LDS_IN = false, bool DC = true,
-          bool B1S = false>
+          bool B1S = false, bool TAP = false>
 __device__ __forceinline__ void back_fused_body(const BackArgs& a, float* ys, int grp, const float* adl = nullptr)
 {
     const BackLane l(a, grp);
@@ -2726,7 +2738,14 @@ __device__ __forceinline__ void back_fused_body(const BackArgs& a, float* ys, in
         for (int m = 0; m < NDC; ++m)
         {
             float u[L];
-            au.step(ag.step(m, pre.step(xin[m], m), l, A), u);
+            if constexpr (TAP)
+            {
+                const float t = au.step_dec(ag.step(m, pre.step(xin[m], m), l, A));
+                if (l.live) a.tap[(size_t)l.c * a.Nd + call * NDC + m] = t;
+                au.interp(t, u);
+            }
+            else
+                au.step(ag.step(m, pre.step(xin[m], m), l, A), u);
 #pragma unroll
             for (int j = 0; j < L; ++j) yl[m * L + j] = ou.step(aa.step(u[j], j));
         }
@@ -2746,17 +2765,18 @@ __device__ __forceinline__ void back_fused_body(const BackArgs& a, float* ys, in
 // DC: the AGC removes DC (AM / SAM; for the demodulator-free bodies only after an AM / SAM
 // demodulator that ran in rx_notch) -- a separate kernel instance for the SSB / CW / DIGI back end
 // without it (the select form cost its f64 arithmetic on every sample)
-template <int PRE, int AA, int L, int PH, int W, int DM, bool CW, bool LDS_IN = false, bool DC = true>
+template <int PRE, int AA, int L, int PH, int W, int DM, bool CW, bool LDS_IN = false, bool DC = true, bool TAP = false>
 __device__ __forceinline__ void back_fused_agc(const BackArgs& a, float* ys, int grp, const float* adl = nullptr)
 {
-    if (a.plan->agc.mode == 5) back_fused_body<PRE, AA, L, PH, W, DM, false, CW, LDS_IN, DC>(a, ys, grp, adl);
-    else back_fused_body<PRE, AA, L, PH, W, DM, true, CW, LDS_IN, DC>(a, ys, grp, adl);
+    if (a.plan->agc.mode == 5) back_fused_body<PRE, AA, L, PH, W, DM, false, CW, LDS_IN, DC, false, TAP>(a, ys, grp, adl);
+    else back_fused_body<PRE, AA, L, PH, W, DM, true, CW, LDS_IN, DC, false, TAP>(a, ys, grp, adl);
 }
 
 // FORM 0: the launch's AGC / CW flags dispatched inside the kernel (its registers are the
 // largest body's: 199 VGPRs at P48, 2 waves per SIMD).  FORM 1: AGC on, CW off only (the SSB /
 // DIGI default, the north-star chain), one body with biquad_1's taps in SGPRs: 160 VGPRs at P48,
-// no scratch, 3 waves per SIMD.
+// no scratch, 3 waves per SIMD.  FORM 2: FORM 0 with the digital-mode tap (BackArgs::tap), the
+// launches of a handle with uhsdr_rx_set_digi_tap only.
 // (the compiler's resource report: the 24 ksps bodies with a pre-filter lattice need 207-220
 // VGPRs at FORM 0 and spill to scratch at 3 waves, so they keep 2)
 __host__ __device__ constexpr int fused1_waves(int pre, int L) { return (L == 2 && pre > 0) ? 2 : 3; }
@@ -2768,6 +2788,12 @@ __attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_S
     if constexpr (FORM == 1)
     {
         back_fused_body<PRE, AA, L, PH, W, DM, true, false, false, DC, true>(a, ys, blockIdx.x);
+        return;
+    }
+    if constexpr (FORM == 2)
+    {
+        if (a.plan->cw_enabled) back_fused_agc<PRE, AA, L, PH, W, DM, true, false, DC, true>(a, ys, blockIdx.x);
+        else back_fused_agc<PRE, AA, L, PH, W, DM, false, false, DC, true>(a, ys, blockIdx.x);
         return;
     }
     if constexpr (L == 4)
@@ -2786,7 +2812,8 @@ __attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_S
 // alternates a FIR phase (VALU + HBM stream) and a recursion phase (dependent VALU chains),
 // waves in different phases share a SIMD and its HBM stream.  The register budget is the back
 // end's (2 waves per SIMD); the front window and the back's output staging share one LDS region.
-template <int T1, int T2, int M, bool DF, int R, bool F, int PRE, int AA, int L, int PH, int W>
+// TAP: the back end also writes BackArgs::tap (instances of their own, 12 ksps)
+template <int T1, int T2, int M, bool DF, int R, bool F, int PRE, int AA, int L, int PH, int W, bool TAP = false>
 __global__ void __launch_bounds__(FRONT_WAVE) __attribute__((amdgpu_waves_per_eu(FUSED_WAVES)))
 rx_chain(FrontArgs fa, BackArgs ba, int front_floats)
 {
@@ -2807,6 +2834,12 @@ rx_chain(FrontArgs fa, BackArgs ba, int front_floats)
                 for (int r = 0; r < RD; ++r) d[(b * RD + r) * CHAIN_ADP] = o[r];
             });
         wave_sync();                                   // the window region is reused by the next pass
+    }
+    if constexpr (TAP)
+    {
+        if (ba.plan->cw_enabled) back_fused_agc<PRE, AA, L, PH, W, DM_NONE, true, true, false, true>(ba, smem, grp, adl);
+        else back_fused_agc<PRE, AA, L, PH, W, DM_NONE, false, true, false, true>(ba, smem, grp, adl);
+        return;
     }
     if constexpr (L == 4)
     {
@@ -3259,7 +3292,21 @@ struct FrontVariant { int t1, t2, m, decim_first; front_fn fn; int R; front_fn f
 // AGC does not remove DC: SSB / CW / DIGI); the same kernel as `fused` for the demodulators
 // fused_ssb: fused_nodc for a launch with the AGC on and the CW decoder off (FORM 1), or null
 // fn_pers: the persistent back end's instance of fn (uhsdr_rx_set_pipelined 3; DM_NONE only)
-struct BackVariant { int pre, aa, L, ph, w, dm; back_fn fn; back_fn fused; back_fn fused_nodc; back_fn fused_ssb; back_fn fn_pers; };
+// fn_tap / fused_tap: the instances that also write the digital-mode tap (12 ksps DM_NONE only)
+struct BackVariant { int pre, aa, L, ph, w, dm; back_fn fn; back_fn fused; back_fn fused_nodc; back_fn fused_ssb; back_fn fn_pers;
+                     back_fn fn_tap; back_fn fused_tap; };
+template <int PRE, int AA, int L, int PH, int W, int DM>
+constexpr back_fn tap_of()
+{
+    if constexpr (DM == DM_NONE && L == 4) return rx_back<PRE, AA, L, PH, W, DM, false, true>;
+    else return nullptr;
+}
+template <int PRE, int AA, int L, int PH, int W, int DM>
+constexpr back_fn fused_tap_of()
+{
+    if constexpr (DM == DM_NONE && L == 4) return rx_back_fused<PRE, AA, L, PH, W, DM, false, 2>;
+    else return nullptr;
+}
 template <int PRE, int AA, int L, int PH, int W, int DM>
 constexpr back_fn pers_of()
 {
@@ -3279,9 +3326,16 @@ constexpr back_fn fused_ssb_of()
     else return nullptr;
 }
 // rx_chain instances: a front family (t1, t2, m, decim_first, R = 8) with a DM_NONE back end
-struct ChainVariant { int t1, t2, m, decim_first, R, pre, aa, L, ph, w; chain_fn fn, fn_fma; };
+struct ChainVariant { int t1, t2, m, decim_first, R, pre, aa, L, ph, w; chain_fn fn, fn_fma, fn_tap, fn_tap_fma; };
+template <int T1, int T2, int M, bool DF, bool F, int PRE, int AA, int PH, int W>
+constexpr chain_fn chain_tap_of()
+{
+    if constexpr (M == 4) return rx_chain<T1, T2, M, DF, 8, F, PRE, AA, M, PH, W, true>;
+    else return nullptr;
+}
 #define CHAIN_V(t1, t2, m, df, pre, aa, ph, w) { t1, t2, m, df, 8, pre, aa, m, ph, w, \
-    rx_chain<t1, t2, m, df, 8, false, pre, aa, m, ph, w>, rx_chain<t1, t2, m, df, 8, true, pre, aa, m, ph, w> }
+    rx_chain<t1, t2, m, df, 8, false, pre, aa, m, ph, w>, rx_chain<t1, t2, m, df, 8, true, pre, aa, m, ph, w>, \
+    chain_tap_of<t1, t2, m, df, false, pre, aa, ph, w>(), chain_tap_of<t1, t2, m, df, true, pre, aa, ph, w>() }
 
 // R = FIR outputs per lane: 16 for large batches (more MACs per window load), 8 for small
 // batches (twice the waves in flight).  fn: reference MAC order (bit-exact); fn_fma: fused MACs
@@ -3414,6 +3468,9 @@ struct uhsdr_rx_s
     float* cw_energy;
     uhsdr_cwdec_handle cwt;  // Morse-to-text decoder (uhsdr_rx_set_cw_text), null when off
     uint8_t* cwt_signal;     // its input [C][N/32] when the user set no signal buffer
+    float* tap;              // user's digital-mode tap [C][Nd] (uhsdr_rx_set_digi_tap), or null
+    uhsdr_rtty_handle rtty;  // RTTY text decoder (uhsdr_rx_set_rtty_text), null when off
+    float* rtty_tap;         // its input [C][Nd] when the user set no tap
     long long calls_done;
     long long front_launches; // oscillator ping-pong parity
     // pipelined mode (uhsdr_rx_set_pipelined): rx_back on a side stream, decimated hand-off
@@ -3793,6 +3850,13 @@ extern "C" uhsdr_status uhsdr_rx_reset(uhsdr_rx_handle h)
         const uhsdr_status cr = uhsdr_cwdec_reset(h->cwt);
         if (cr != UHSDR_OK) return cr;
     }
+    if (h->rtty)
+    {
+        const uhsdr_status cs = uhsdr_rtty_set_stream(h->rtty, h->stream);
+        if (cs != UHSDR_OK) return cs;
+        const uhsdr_status cr = uhsdr_rtty_reset(h->rtty);
+        if (cr != UHSDR_OK) return cr;
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->dec_samples = 0;
     h->calls_done = 0;
@@ -4021,6 +4085,99 @@ static uhsdr_status launch_cw_text(uhsdr_rx_s* h, int cw0, hipStream_t st)
     return uhsdr_cwdec_launch(h->cwt, h->cw_signal ? h->cw_signal : h->cwt_signal, h->cw_blocks_last, h->N / BLK, first, cpb);
 }
 
+// the digital-mode tap exists where the firmware runs its modems (audio_driver.c:2537-2557): a
+// 12 ksps path of the SSB / CW / DIGI back-end family, mono
+static uhsdr_status tap_supported(const uhsdr_rx_s* h, const char* what)
+{
+    const uhsdr_rx_plan& p = h->plan;
+    if (p.decimation_rate != 4 || plan_dm(p) != DM_NONE || p.stereo || p.agc.remove_dc || !h->bv->fn_tap || !h->bv->fused_tap ||
+        (h->cv && !h->cv->fn_tap))
+    {
+        uhsdr_set_error("%s: needs a 12 ksps path of the SSB / CW / DIGI back end, mono (mode %d, decimation %d, stereo %d)",
+                        what, (int)p.dmod_mode, (int)p.decimation_rate, (int)p.stereo);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (tap)
+    {
+        const uhsdr_status ts = tap_supported(h, "digi tap");
+        if (ts != UHSDR_OK) return ts;
+    }
+    float* own = nullptr;
+    if (!tap && h->rtty && !h->rtty_tap)
+    {
+        // the text decoder goes on reading a row: the handle's own
+        if (hipMalloc((void**)&own, sizeof(float) * (size_t)h->C * h->Nd) != hipSuccess)
+        {
+            uhsdr_set_error("digi tap: device allocation failed");
+            return UHSDR_DEVICE_ERROR;
+        }
+    }
+    HIPCHK(sync_all(h));
+    if (own) h->rtty_tap = own;
+    h->tap = tap;
+    return UHSDR_OK;
+}
+
+// the row the TAP kernel instances write, or null: the launch runs the instances without a tap
+static float* tap_row(const uhsdr_rx_s* h) { return h->tap ? h->tap : h->rtty ? h->rtty_tap : nullptr; }
+
+// RTTY text (uhsdr_rtty.hip) on the tap row of every call
+extern "C" uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx,
+                                               int32_t stopbits_idx, int32_t atc_disable, int32_t text_capacity)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    // the firmware decodes RTTY only in DEMOD_DIGI (is_demod_rtty, audio_driver.c:2543)
+    if (h->plan.dmod_mode != UHSDR_DEMOD_DIGI)
+    {
+        uhsdr_set_error("rtty text: needs demodulator mode DIGI, not mode %d", (int)h->plan.dmod_mode);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    const uhsdr_status ts = tap_supported(h, "rtty text");
+    if (ts != UHSDR_OK) return ts;
+    uhsdr_rtty_handle dec = nullptr;
+    float* row = nullptr;
+    if (enable)
+    {
+        // (argument errors before anything changes)
+        const uhsdr_status st = uhsdr_rtty_create(h->C, shift_idx, speed_idx, stopbits_idx, atc_disable, text_capacity,
+                                                  h->stream, &dec);
+        if (st != UHSDR_OK) return st;
+        if (!h->tap && hipMalloc((void**)&row, sizeof(float) * (size_t)h->C * h->Nd) != hipSuccess)
+        {
+            uhsdr_set_error("rtty text: device allocation failed");
+            (void)uhsdr_rtty_destroy(dec);
+            return UHSDR_DEVICE_ERROR;
+        }
+    }
+    HIPCHK(sync_all(h));
+    if (h->rtty) (void)uhsdr_rtty_destroy(h->rtty);
+    if (h->rtty_tap) (void)hipFree(h->rtty_tap);
+    h->rtty = dec;
+    h->rtty_tap = row;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_rtty_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total)
+{
+    if (!h || !h->rtty) { uhsdr_set_error("rtty text is off (uhsdr_rx_set_rtty_text)"); return UHSDR_ARGUMENT_ERROR; }
+    return uhsdr_rtty_outputs(h->rtty, text, total);
+}
+
+// the call's Nd tap samples through the RTTY decoder, after the kernel that wrote them and on its stream
+static uhsdr_status launch_rtty_text(uhsdr_rx_s* h, hipStream_t st)
+{
+    if (!h->rtty) return UHSDR_OK;
+    const uhsdr_status ss = uhsdr_rtty_set_stream(h->rtty, st);
+    if (ss != UHSDR_OK) return ss;
+    return uhsdr_rtty_process(h->rtty, tap_row(h), h->Nd, h->Nd);
+}
+
 extern "C" uhsdr_status uhsdr_rx_set_clip_output(uhsdr_rx_handle h, uint32_t* clip)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
@@ -4139,6 +4296,7 @@ static BackArgs back_args(uhsdr_rx_s* h, float* adec, float* adec_q, float* audi
     ba.cw_energy = h->bs.cw ? h->cw_energy : nullptr;
     ba.cw_count0 = h->cw_count;
     ba.cw_bmax = h->cw_bmax;
+    ba.tap = tap_row(h);
     {
         const int slots = NOTCH_DELAY / (BLK / h->plan.decimation_rate);
         ba.notch_slot0 = (int)(h->calls_done % slots);
@@ -4212,7 +4370,8 @@ static uhsdr_status chain_call(uhsdr_rx_s* h, const int32_t* iq, float* audio, f
     const FrontArgs fa = front_args(h, iq, 0, nullptr, nullptr);
     const BackArgs ba = back_args(h, nullptr, nullptr, audio, audio0, dst);
     time_mark(h, K_CHAIN, 0);
-    hipLaunchKernelGGL(fma ? h->cv->fn_fma : h->cv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(FRONT_WAVE),
+    const chain_fn cfn = ba.tap ? (fma ? h->cv->fn_tap_fma : h->cv->fn_tap) : fma ? h->cv->fn_fma : h->cv->fn;
+    hipLaunchKernelGGL(cfn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(FRONT_WAVE),
                        chain_lds(h), h->stream, fa, ba, (int)chain_front_floats(h));
     HIPCHK(hipGetLastError());
     time_mark(h, K_CHAIN, 1);
@@ -4265,7 +4424,8 @@ static RxRoute route_call(const uhsdr_rx_s* h)
             h->bv->dm == DM_NONE && r.bgroups <= h->hand.dflag_grid;
     r.gc = h->hand.gcnt + (size_t)r.par * r.bgroups * CNT_PITCH;
     // persistent back end (PersistCtl): the wave pipeline's skewed form, calls of 8+ sub-calls
-    r.pm = r.dfl && h->pers && h->hand.skew && h->N / BLK >= 2 * BACK_SKEW && !h->bs.cw &&
+    // (not with the digital-mode tap, whose rows belong to the launch's own call: mode 3 runs as mode 2)
+    r.pm = r.dfl && h->pers && h->hand.skew && h->N / BLK >= 2 * BACK_SKEW && !h->bs.cw && !tap_row(h) &&
            r.bgroups <= PC_MAX_GROUPS && h->bv->fn_pers;
     r.seq = (unsigned)r.pk;
     return r;
@@ -4373,7 +4533,7 @@ static void handoff_args(const uhsdr_rx_s* h, const RxRoute& r, BackArgs& bk)
     // joins the side stream first, so no later front starts before this launch ends).  Not
     // with the CW decoder (its per-call outputs belong to the launch's own call) or calls of
     // fewer than BACK_SKEW 32-frame blocks.
-    if (h->hand.skew && h->N / BLK >= BACK_SKEW && !h->bs.cw)
+    if (h->hand.skew && h->N / BLK >= BACK_SKEW && !h->bs.cw && !bk.tap)
     {
         const int parn = (int)((r.pk + 1) % PIPE_BUFS);
         bk.adec_next = parn ? h->adecp[parn - 1] : h->adec;
@@ -4452,6 +4612,10 @@ static size_t back_launch_lds(uhsdr_rx_s* h, const RxRoute& r)
                 hipFuncSetAttribute((const void*)h->bv->fn_pers, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)LDS_PER_CU) != hipSuccess)
                 h->hand.back_attr = -1;
+            if (h->hand.back_attr > 0 && h->bv->fn_tap &&
+                hipFuncSetAttribute((const void*)h->bv->fn_tap, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)LDS_PER_CU) != hipSuccess)
+                h->hand.back_attr = -1;
             (void)hipGetLastError();
         }
         if (h->hand.back_attr > 0) return LDS_PER_CU - 4096;
@@ -4471,7 +4635,7 @@ static uhsdr_status launch_back(uhsdr_rx_s* h, const RxRoute& r, const BackArgs&
         hipLaunchKernelGGL(h->nv->fn, dim3((h->C + BACK_CH - 1) / BACK_CH), dim3(BACK_CH), 0, bst, bk);
         HIPCHK(hipGetLastError());
     }
-    const back_fn bfn = r.fused ? fused_back_fn(h) : r.pm ? h->bv->fn_pers : h->bv->fn;
+    const back_fn bfn = r.fused ? (bk.tap ? h->bv->fused_tap : fused_back_fn(h)) : r.pm ? h->bv->fn_pers : bk.tap ? h->bv->fn_tap : h->bv->fn;
     // (the wave pipeline: its role waves and BACK_TAILS tail waves; rx_fm: its two; the fused kernels: one)
     const int bwaves = r.fused ? 1 : h->bv->dm == DM_FM ? back_roles(DM_FM) : back_roles(h->bv->dm) + back_tails(h->bv->dm);
     const dim3 bgrid((h->C + BACK_CH - 1) / BACK_CH), bblock(bwaves * BACK_CH);
@@ -4504,6 +4668,7 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
     {
         RXSTEP(chain_call(h, iq, audio, audio0, dst, fma));
         RXSTEP(launch_cw_text(h, cw0, h->stream));
+        RXSTEP(launch_rtty_text(h, h->stream));
     }
     else
     {
@@ -4519,6 +4684,7 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
         if (r.pm) RXSTEP(pers_grant(h, r, bk, launch));
         RXSTEP(launch_back(h, r, bk, launch));
         RXSTEP(launch_cw_text(h, cw0, back_stream(h)));
+        RXSTEP(launch_rtty_text(h, back_stream(h)));
         if (h->pipelined) h->pipe_calls += 1;
         if (r.side) h->side_dirty = 1;
         h->main_back = !r.side;
@@ -4794,6 +4960,8 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
     (void)sync_all(h);
     if (h->cwt) (void)uhsdr_cwdec_destroy(h->cwt);
     if (h->cwt_signal) (void)hipFree(h->cwt_signal);
+    if (h->rtty) (void)uhsdr_rtty_destroy(h->rtty);
+    if (h->rtty_tap) (void)hipFree(h->rtty_tap);
     if (h->side)
     {
         (void)hipEventDestroy(h->ev_front);

@@ -16,7 +16,8 @@ static const FrontVariant kFront[] = {
 #undef FRONT_ST
 
 #define BACK_V(pre, aa, L, ph, w, dm) { pre, aa, L, ph, w, dm, rx_back<pre, aa, L, ph, w, dm>, rx_back_fused<pre, aa, L, ph, w, dm>, \
-    fused_nodc_of<pre, aa, L, ph, w, dm>(), fused_ssb_of<pre, aa, L, ph, w, dm>(), pers_of<pre, aa, L, ph, w, dm>() }
+    fused_nodc_of<pre, aa, L, ph, w, dm>(), fused_ssb_of<pre, aa, L, ph, w, dm>(), pers_of<pre, aa, L, ph, w, dm>(), \
+    tap_of<pre, aa, L, ph, w, dm>(), fused_tap_of<pre, aa, L, ph, w, dm>() }
 static const BackVariant kBack[] = {
     // SSB / CW / DIGI
     BACK_V(10, 6, 4, 1, 49, DM_NONE), BACK_V(10, 0, 4, 4, 49, DM_NONE), BACK_V(0, 0, 2, 8, 97, DM_NONE),

@@ -50,6 +50,8 @@ class RxChain:
         _abi.check(self.lib.uhsdr_rx_reset(self.handle), "uhsdr_rx_reset")
         if getattr(self, "_cw_text", None) is not None:
             self._cw_text.seen[:] = 0
+        if getattr(self, "_rtty_text", None) is not None:
+            self._rtty_text.seen[:] = 0
 
     def _shape_ok(self, t, last):
         shp = tuple(t.shape)
@@ -149,6 +151,42 @@ class RxChain:
     @property
     def cw_text_outputs(self):
         return getattr(self, "_cw_text", None)
+
+    def set_digi_tap(self, tap=None) -> None:
+        """Digital-mode tap of the following calls: f32 [C][N/4] on the device, a_buffer[0] after
+        biquad_1 (uhsdr_rx_set_digi_tap); 12 ksps SSB / CW / DIGI paths only.  None turns it off."""
+        if tap is not None and (tuple(tap.shape) != (self.channels, self.frames // 4) or not tap.is_floating_point()
+                                or tap.element_size() != 4 or not tap.is_contiguous()):
+            raise ValueError("tap must be a contiguous float32 tensor [C][N/4]")
+        _abi.check(self.lib.uhsdr_rx_set_digi_tap(self.handle, C.c_void_p(tap.data_ptr() if tap is not None else 0)),
+                   "uhsdr_rx_set_digi_tap")
+        self._tap = tap   # keep the tensor alive
+
+    def set_rtty_text(self, enable: bool = True, shift: int = 1, speed: int = 0, stopbits: int = 1,
+                      atc_disable: bool = False, text_capacity: int = 64) -> None:
+        """RTTY decoding of the tap samples of every following call (uhsdr_rx_set_rtty_text): only
+        in dmod_mode DIGI on a 12 ksps path.  Indices as uhsdr_amd.rtty."""
+        _abi.check(self.lib.uhsdr_rx_set_rtty_text(self.handle, int(bool(enable)), int(shift), int(speed), int(stopbits),
+                                                   int(bool(atc_disable)), int(text_capacity)), "uhsdr_rx_set_rtty_text")
+        self._rtty_text = None
+        if enable:
+            from .rtty import RttyOutputs
+            p = [C.c_void_p() for _ in range(2)]
+            _abi.check(self.lib.uhsdr_rx_rtty_text_outputs(self.handle, C.byref(p[0]), C.byref(p[1])),
+                       "uhsdr_rx_rtty_text_outputs")
+            self._rtty_text = RttyOutputs(self.lib, self.channels, int(text_capacity), True, *(x.value for x in p))
+
+    def rtty_text(self):
+        """Per channel, the bytes decoded since the last read (synchronises).  With
+        .rtty_text_outputs.read() the text ring and the totals are available as arrays."""
+        if getattr(self, "_rtty_text", None) is None:
+            raise RuntimeError("rtty text is off: set_rtty_text() first")
+        self.synchronize()
+        return self._rtty_text.new_text()
+
+    @property
+    def rtty_text_outputs(self):
+        return getattr(self, "_rtty_text", None)
 
     @property
     def cw_blocks_max(self) -> int:

@@ -320,3 +320,146 @@ def cw_text_iq(channels, start: int, nframes: int, text: str, wpm: float = 20.0,
         ni, nq = _noise(channels, start, nframes, noise_sigma)
         i_sig, q_sig = i_sig + ni, q_sig + nq
     return _frames(i_sig, q_sig)
+
+
+# ITA2 (Baudot-Murray) as the RTTY decoder prints it: code -> character in the letters and the
+# figures case; 27 selects figures, 31 letters, and 0, 2, 4 and 8 read the same in both
+BAUDOT_LETTERS = "\0E\nA SIU\rDRJNFCKTZLWHYPQOBG\x0eMXV\x0f"
+BAUDOT_FIGURES = "\0" "3\n- \a87\r$4',!:(5\")2#6019?&\x0e./;\x0f"
+BAUDOT_FIGS, BAUDOT_LTRS = 27, 31
+RTTY_SHIFTS = (85.0, 170.0, 200.0, 425.0, 450.0, 850.0)      # shift_idx 0 .. 5
+RTTY_SPEEDS = (45.45, 50.0)                                  # speed_idx 0 .. 1
+RTTY_STOPBITS = (1.0, 1.5, 2.0)                              # stopbits_idx 0 .. 2
+RTTY_MARK = 915.0
+
+
+def baudot_codes(text: str, close: bool = False):
+    """The 5-bit codes that send `text` (upper-cased), starting in the letters case, with a FIGS
+    or LTRS code wherever the case changes; `close` ends in the letters case, so the message can
+    be repeated."""
+    codes, figs = [], False
+    for ch in text.upper():
+        in_l, in_f = BAUDOT_LETTERS.find(ch), BAUDOT_FIGURES.find(ch)
+        if ch in "\x0e\x0f" or (in_l < 0 and in_f < 0):
+            raise ValueError(f"{ch!r} has no Baudot code")
+        if (in_f if figs else in_l) < 0:
+            figs = not figs
+            codes.append(BAUDOT_FIGS if figs else BAUDOT_LTRS)
+        codes.append(in_f if figs else in_l)
+    if close and figs:
+        codes.append(BAUDOT_LTRS)
+    return codes
+
+
+def baudot_bits(text: str, stopbits: float = 1.5, close: bool = False):
+    """(level uint8 [k], length float [k]): the line as runs of mark (1) and space (0), lengths in
+    bit times: per code a start bit (space), five data bits, lowest first, and `stopbits` of mark."""
+    level, length = [], []
+    for code in baudot_codes(text, close):
+        level += [0] + [(code >> b) & 1 for b in range(5)] + [1]
+        length += [1.0] * 6 + [float(stopbits)]
+    return np.array(level, np.uint8), np.array(length, np.float64)
+
+
+def _rtty_line(bits, baud: float, rate: float):
+    """mark / space per sample of one pass of the message at `rate` samples per second"""
+    level, length = bits
+    edges = np.rint(np.cumsum(np.concatenate([[0.0], length * (rate / baud)]))).astype(np.int64)
+    return np.repeat(level, np.diff(edges)).astype(np.uint8)
+
+
+def rtty_audio(text, shift: float = 170.0, baud: float = 45.45, stopbits: float = 1.5, amplitude: float = 1000.0,
+               noise_sigma: float = 0.0, fade: str | None = None, fade_depth: float = 0.9, fade_period: int = 36000,
+               lead: int = 6000, tail: int = 6000, offset: int = 0, seed: int = 0, silence: int = 0,
+               rate: float = 12000.0) -> np.ndarray:
+    """12 ksps float32 audio of an RTTY transmission, the decoder's stand-alone input: continuous
+    phase FSK, mark at 915 Hz, space at 915 Hz + `shift`, idle mark for `lead` samples before and
+    `tail` after the message.  `text` is a string or the (level, length) runs of baudot_bits.
+    `fade` "mark" or "space" lets that tone's amplitude swing between 1 and 1 - `fade_depth`
+    every `fade_period` samples; `noise_sigma` adds white noise (counter-based, `seed`); the
+    first `offset` samples are dropped, so a stream can start mid-character, and `silence` samples
+    of exact zero follow the tail.  Samples are rounded to integers."""
+    bits = baudot_bits(text, stopbits) if isinstance(text, str) else text
+    line = np.concatenate([np.ones(lead, np.uint8), _rtty_line(bits, baud, rate), np.ones(tail, np.uint8)])
+    freq = np.where(line != 0, RTTY_MARK, RTTY_MARK + shift)
+    phase = 2.0 * np.pi / rate * np.concatenate([[0.0], np.cumsum(freq)[:-1]])
+    gain = np.full(len(line), float(amplitude))
+    if fade:
+        swing = 1.0 - fade_depth * 0.5 * (1.0 - np.cos(2.0 * np.pi * np.arange(len(line)) / fade_period))
+        gain = np.where((line != 0) == (fade == "mark"), gain * swing, gain)
+    s = gain * np.sin(phase)
+    if noise_sigma > 0:
+        s = s + _noise(np.array([1 << 16 | seed], np.int64), 0, len(line), noise_sigma)[0][0]
+    return np.concatenate([np.rint(s)[offset:], np.zeros(silence)]).astype(np.float32)
+
+
+def rtty_iq(channels, start: int, nframes: int, text: str, shift: float = 170.0, baud: float = 45.45, stopbits: float = 1.5,
+            noise_sigma: float = 30.0, carrier: float = 12000.0, amplitude: float = 1500.0, lead: int = 24000,
+            fade: str | None = None, fade_depth: float = 0.9, fade_period: int = 144000):
+    """48 ksps I/Q of an RTTY signal on the upper side of `carrier`: mark at +915 Hz, space at
+    +915 Hz + `shift`, `text` repeated for ever after `lead` frames of idle mark plus a per-channel
+    start offset of up to one second; continuous phase, optional fading of the mark or space
+    tone, plus noise.  The RTTY text decoder's input through the RX chain (DEMOD_DIGI)."""
+    channels = np.asarray(channels, dtype=np.int64)
+    ch = channels.astype(np.uint64)
+    base = (np.uint64(SEED_BASE) + ch) << np.uint64(20)
+    delay = lead + np.floor(FS * _uniform(base + np.uint64(14))).astype(np.int64)
+    ph_c = 2.0 * np.pi * _uniform(base + np.uint64(15))
+    line = _rtty_line(baudot_bits(text, stopbits, close=True), baud, FS)
+    period = len(line)
+    spaces = np.concatenate([[0], np.cumsum(line == 0)]).astype(np.int64)     # space frames before frame k of a pass
+    n = np.arange(start, start + nframes, dtype=np.int64)
+    i_sig = np.empty((len(channels), nframes))
+    q_sig = np.empty((len(channels), nframes))
+    for k in range(len(channels)):
+        rel = n - int(delay[k])
+        on = rel >= 0
+        r = np.where(on, rel, 0)
+        nspace = np.where(on, (r // period) * spaces[period] + spaces[r % period], 0)
+        mark = np.where(on, line[r % period] != 0, True)
+        ph = 2.0 * np.pi / FS * ((carrier + RTTY_MARK) * n.astype(np.float64) + shift * nspace.astype(np.float64)) + ph_c[k]
+        gain = np.full(nframes, float(amplitude))
+        if fade:
+            swing = 1.0 - fade_depth * 0.5 * (1.0 - np.cos(2.0 * np.pi * n / fade_period))
+            gain = np.where(mark == (fade == "mark"), gain * swing, gain)
+        i_sig[k], q_sig[k] = gain * np.cos(ph), gain * np.sin(ph)
+    if noise_sigma > 0:
+        ni, nq = _noise(channels, start, nframes, noise_sigma)
+        i_sig, q_sig = i_sig + ni, q_sig + nq
+    return _frames(i_sig, q_sig)
+
+
+def rtty_fixture(path: str) -> dict:
+    """A recorded stand-alone RTTY case (an npz of tools/rtty/make_rtty_golden.py) with its input
+    regenerated from the recorded arguments and checked against the recorded crc32: the file's
+    arrays plus `audio` (float32, read-only) and `config` (shift, speed, stop bits, atc_disable)."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    text = (g["bits_level"], g["bits_length"]) if len(g["bits_level"]) else str(g["message"])
+    audio = rtty_audio(text, **json.loads(str(g["gen"])))
+    if len(audio) != int(g["samples"]) or zlib.crc32(audio.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    audio.setflags(write=False)
+    g["audio"] = audio
+    g["config"] = (int(g["shift_idx"]), int(g["speed_idx"]), int(g["stopbits_idx"]), int(g["atc_disable"]))
+    return g
+
+
+def rtty_chain_fixture(path: str) -> dict:
+    """A recorded RTTY case through the receive chain (rtty_chain_*.npz): the file's arrays plus
+    `iq` (int32 [frames][2], one channel, read-only) regenerated from the recorded arguments of
+    rtty_iq and checked against the recorded crc32, and `config` as above."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    gen = json.loads(str(g["gen"]))
+    iq = np.ascontiguousarray(rtty_iq([gen.pop("channel")], 0, gen.pop("nframes"), gen.pop("text"), **gen)[0], dtype=np.int32)
+    if zlib.crc32(iq.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    iq.setflags(write=False)
+    g["iq"] = iq
+    g["config"] = (int(g["shift_idx"]), int(g["speed_idx"]), int(g["stopbits_idx"]), int(g["atc_disable"]))
+    return g
