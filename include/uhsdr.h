@@ -382,8 +382,9 @@ uhsdr_status uhsdr_rx_set_front_block(uhsdr_rx_handle h, int32_t outputs_per_lan
  * red indicator and the auto RF-gain trigger / release.  The firmware's UI reads and clears
  * them; here the kernels OR the bits of every frame they process into clip[c] (device memory,
  * [C] uint32, the caller zeroes it and clears it after reading).  NULL (default) = not computed.
- * The magnitude is taken as unsigned, so a full-scale negative sample (INT32_MIN, where the
- * reference's abs() is undefined) counts as a clip. */
+ * The level is a signed int32 as in the reference: abs(INT32_MIN) wraps to INT32_MIN, the shift
+ * keeps it negative, and so a sample of exactly -2^31 raises no flag (the compiled reference's
+ * behaviour); -(2^31-1) and 2^31-1 raise all three. */
 #define UHSDR_ADC_CLIP          1
 #define UHSDR_ADC_HALF_CLIP     2
 #define UHSDR_ADC_QUARTER_CLIP  4

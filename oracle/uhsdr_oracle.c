@@ -658,9 +658,10 @@ static void rx_call(const uhsdr_rx_plan* p, uo_rx_state* s, const int32_t* iq, f
     {
         /* ADC clip indicators on the I sample, |l| >> IQ_BIT_SHIFT against ADC_CLIP_WARN_THRESHOLD
            = 4096 and its quarter / half (audio_driver.c:2660-2676, audio_driver.h:81); the
-           magnitude is taken unsigned, so a full-scale negative sample counts as a clip */
+           level is a signed int32: abs() of -2^31 wraps to -2^31 and the arithmetic shift keeps it
+           negative, so that one sample raises no flag, as in the compiled reference */
         const uint32_t v = (uint32_t)iq[2 * i];
-        const uint32_t level = ((v & 0x80000000u) ? 0u - v : v) >> 16;
+        const int32_t level = (int32_t)((v & 0x80000000u) ? 0u - v : v) >> 16;
         if (level > 4096 / 4) s->clip |= UHSDR_ADC_QUARTER_CLIP;
         if (level > 4096 / 2) s->clip |= UHSDR_ADC_HALF_CLIP;
         if (level > 4096) s->clip |= UHSDR_ADC_CLIP;

@@ -17,7 +17,10 @@ plus tests/golden/filter_paths.json (FilterPathInfo[], audio_filter.c:147-922, a
 float bits), the TX / spectrum / CW fixtures (tx_*, spec_*, cw_*.npz) and
 tests/golden/cmsis_vectors.npz (CMSIS-DSP f32 call sequences, dump=cmsis, oracle/ref/ref_cmsis.c),
 and the status fixtures (st_*.npz: per-call ADC clip flags and twin-peaks state over >130k
-frames; the input is regenerated from uhsdr_amd.synth and checked by its crc32).  Only runs where /root/reference exists (build container); the fixtures
+frames; the input is regenerated from uhsdr_amd.synth and checked by its crc32), the clip flags at the rails (cliprail_*.npz) and
+the edge-input fixtures (rxedge_*.npz, txedge_*.npz: EDGE_CONFIGS below; --only edge, rxedge,
+txedge or one file's name without .npz; written with fixed zip timestamps, so a rerun reproduces
+the committed bytes).  Only runs where /root/reference exists (build container); the fixtures
 are committed and the GPU box never needs the reference.
 
     python tests/golden/make_golden.py [--only NAME]
@@ -287,6 +290,177 @@ def make_status(name: str):
     print(f"st_{name:12s} calls={calls} final twinpeaks={final} clip calls={[(clip[c] != 0).sum() for c in range(STATUS_NCH)]}")
 
 
+def save_npz(path: str, **arrays):
+    """np.savez_compressed with fixed zip timestamps, so a rerun gives the same bytes"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            zi = zipfile.ZipInfo(k + ".npy", (1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(zi, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+# The clip flags at the rails (audio_driver.c:2662, abs(l) >> 16 as a signed int): synth.clip_rail_iq
+# holds I at INT32_MIN, -(2^31-1) and INT32_MAX for 8 calls each; the flags per call, read and cleared
+CLIP_RAIL_CONFIGS = {"p48_usb": {"mode": 0, "path": 48}}
+CLIP_RAIL_NCH = 2
+
+
+def make_clip_rail(name: str):
+    import zlib
+    args = CLIP_RAIL_CONFIGS[name]
+    nfr = synth.CLIP_RAIL_FRAMES
+    iq = synth.clip_rail_iq(np.arange(CLIP_RAIL_NCH), 0, nfr)
+    clip = np.empty((CLIP_RAIL_NCH, nfr // 32), np.uint8)
+    for c in range(CLIP_RAIL_NCH):
+        with tempfile.TemporaryDirectory() as td:
+            fin, fa, fc = (os.path.join(td, x) for x in ("in.bin", "a.bin", "c.bin"))
+            iq[c].astype(np.int32).tofile(fin)
+            cmd = [REF, f"in={fin}", f"n={nfr}", f"out_a={fa}", f"out_clip={fc}"]
+            subprocess.run(cmd + [f"{k}={v}" for k, v in args.items()], check=True)
+            clip[c] = np.fromfile(fc, dtype=np.uint8)
+    save_npz(os.path.join(HERE, f"cliprail_{name}.npz"), clip=clip, frames=nfr,
+                        iq_crc32=zlib.crc32(np.ascontiguousarray(iq).tobytes()), args=json.dumps(args))
+    print(f"cliprail_{name}: flags per call, channel 0: {clip[0].tolist()}")
+
+
+# Edge inputs (synth.edge_iq / edge_audio: silence, signal / silence / signal, full scale, low
+# bits): name -> (uhsdr_ref args, base generator, its kwargs); one row per kind of synth.EDGE_KINDS,
+# channel 0, synth.EDGE_FRAMES frames.  Stored like the st_* fixtures: no input (regenerated, crc32
+# checked), per 32-frame call a crc32 of a1, a0 and dst, and whole samples in three windows --
+# frames [0, 4096), 2048 frames from the row's first denormal a1 sample (from frame 4096 where
+# the row has none), and the last 6144 frames.
+EDGE_CONFIGS = {
+    "p48_usb": ({"mode": 0, "path": 48}, "ssb_iq", {}),
+    "p48_agcoff": ({"mode": 0, "path": 48, "agc_mode": 5}, "ssb_iq", {}),
+    "p48_notch": ({"mode": 0, "path": 48, "dsp": 4}, "ssb_iq", {}),
+    "p48_eq": ({"mode": 0, "path": 48, "dsp": 0x30, "bass": -6, "treble": 4, "notch": 1200, "peak": 900}, "ssb_iq", {}),
+    "p48_iqauto": ({"mode": 0, "path": 48, "iq_auto": 1}, "ssb_iq", {}),
+    "p35_usb": ({"mode": 0, "path": 35}, "ssb_iq", {}),
+    "p55_usb": ({"mode": 0, "path": 55}, "ssb_iq", {}),
+    "p4_cw": ({"mode": 2, "path": 4}, "ssb_iq", {}),
+    "p48_ssbstereo": ({"mode": 7, "path": 48, "stereo": 1}, "ssb_iq", {}),
+    "p70_am": ({"mode": 3, "path": 70}, "am_iq", {}),
+    "p70_sam": ({"mode": 4, "path": 70}, "am_iq", {}),
+    "p1_fm_sql0": ({"mode": 5, "path": 1, "sql": 0}, "fm_iq", {}),
+    "p1_fm": ({"mode": 5, "path": 1}, "fm_iq", {}),
+    "p35_lsb_mchf_spkr30": ({"mode": 1, "path": 35, "board": 1, "spkr": 30}, "ssb_iq", {"lsb": True}),
+}
+EDGE_CW = ("p4_cw",)                   # out_cw / out_cws recorded too
+EDGE_TX_CONFIGS = {k: TX_CONFIGS[k] for k in ("usb", "usb_comp_hi", "fm_subtone", "am")}
+EDGE_WINDOWS = (4096, 2048, 6144)      # head, from the first denormal, tail
+FLT_MIN = np.float32(1.17549435e-38)
+
+
+def edge_call_crcs(x: np.ndarray) -> np.ndarray:
+    """crc32 of every 32-frame call of x [n, ...]"""
+    import zlib
+    b = np.ascontiguousarray(x).reshape(x.shape[0] // 32, -1).view(np.uint8)
+    return np.array([zlib.crc32(r) for r in b], np.uint32)
+
+
+def edge_window_starts(ref: np.ndarray):
+    """starts of the three stored windows of a row whose denormal-checked output is ref [n]"""
+    n = ref.shape[0]
+    a = np.abs(ref)
+    den = np.flatnonzero((a > 0) & (a < FLT_MIN))
+    first = int(den[0]) if len(den) else EDGE_WINDOWS[0]
+    return np.array([0, min(first, n - EDGE_WINDOWS[1]), n - EDGE_WINDOWS[2]], np.int64), len(den)
+
+
+def edge_windows(x: np.ndarray, starts) -> np.ndarray:
+    return np.concatenate([x[s:s + w] for s, w in zip(starts, EDGE_WINDOWS)])
+
+
+def _edge_rx_row(job):
+    args, iq, cw = job
+    n = iq.shape[0]
+    with tempfile.TemporaryDirectory() as td:
+        fin, fa, fd, fa0, fcw, fs = (os.path.join(td, x) for x in ("in.bin", "a.bin", "d.bin", "a0.bin", "cw.bin", "s.bin"))
+        iq.astype(np.int32).tofile(fin)
+        cmd = [ref_bin(args), f"in={fin}", f"n={n}", f"out_a={fa}", f"out_dst={fd}", f"out_a0={fa0}"]
+        if cw:
+            cmd += [f"out_cw={fcw}", f"out_cws={fs}"]
+        subprocess.run(cmd + [f"{k}={v}" for k, v in args.items()], check=True)
+        out = [np.fromfile(fa, dtype=np.float32), np.fromfile(fa0, dtype=np.float32),
+               np.fromfile(fd, dtype=np.int32).reshape(n, 2)]
+        if cw:
+            out += [np.fromfile(fs, dtype=np.uint8), np.fromfile(fcw, dtype=np.float32)]
+    assert out[0].shape == out[1].shape == (n,), "short output from uhsdr_ref"
+    return out
+
+
+def make_edge_rx(name: str):
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    args, base, kw = EDGE_CONFIGS[name]
+    n = synth.EDGE_FRAMES
+    rows = [synth.edge_iq(k, [0], 0, n, base=getattr(synth, base), **kw)[0] for k in synth.EDGE_KINDS]
+    cw = name in EDGE_CW
+    with ThreadPoolExecutor(len(rows)) as ex:
+        outs = list(ex.map(_edge_rx_row, [(args, r, cw) for r in rows]))
+    d = {"crc_a1": [], "crc_a0": [], "crc_dst": [], "win_start": [], "win_a1": [], "win_a0": [], "win_dst": [],
+         "denormal_a1": [], "nonfinite": [], "peak_a1": []}
+    for a1, a0, dst, *_ in outs:
+        starts, nden = edge_window_starts(a1)
+        d["crc_a1"].append(edge_call_crcs(a1))
+        d["crc_a0"].append(edge_call_crcs(a0))
+        d["crc_dst"].append(edge_call_crcs(dst))
+        d["win_start"].append(starts)
+        d["win_a1"].append(edge_windows(a1, starts))
+        d["win_a0"].append(edge_windows(a0, starts))
+        d["win_dst"].append(edge_windows(dst, starts))
+        d["denormal_a1"].append(nden)
+        d["nonfinite"].append(int((~np.isfinite(a1)).sum() + (~np.isfinite(a0)).sum()))
+        d["peak_a1"].append(np.abs(a1).max())
+    d = {k: np.stack(v) if isinstance(v[0], np.ndarray) else np.array(v) for k, v in d.items()}
+    # a_buffer[0] is stored whole only where it is not a copy of a_buffer[1] (stereo, mcHF line out)
+    if all(np.array_equal(o[0].view(np.uint32), o[1].view(np.uint32)) for o in outs):
+        del d["win_a0"], d["crc_a0"]
+    if cw:
+        d["cw_signal"] = np.stack([o[3] for o in outs])
+        d["cw_energy"] = np.stack([o[4] for o in outs])
+    save_npz(os.path.join(HERE, f"rxedge_{name}.npz"), **d, frames=n, kinds=json.dumps(synth.EDGE_KINDS),
+                        iq_crc32=np.array([zlib.crc32(np.ascontiguousarray(r).tobytes()) for r in rows], np.uint32),
+                        base=base, base_kw=json.dumps(kw), args=json.dumps(args))
+    size = os.path.getsize(os.path.join(HERE, f"rxedge_{name}.npz"))
+    print(f"rxedge_{name:20s} {size:7d} B  denormal a1 {d['denormal_a1'].tolist()}  peak|a1| "
+          f"{[float(f'{p:.4g}') for p in d['peak_a1']]}")
+
+
+def _edge_tx_row(job):
+    args, audio = job
+    return run_ref(args, audio)
+
+
+def make_edge_tx(name: str):
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+    args = dict(EDGE_TX_CONFIGS[name], tx=1)
+    n = synth.EDGE_AUDIO_FRAMES
+    rows = [synth.edge_audio(k, [0], 0, n)[0] for k in synth.EDGE_AUDIO_KINDS]
+    with ThreadPoolExecutor(len(rows)) as ex:
+        outs = list(ex.map(_edge_tx_row, [(args, r) for r in rows]))
+    d = {"crc_a0": [], "crc_iq": [], "win_start": [], "win_a0": [], "win_iq": [], "denormal_a0": [], "nonfinite": [],
+         "peak_a0": []}
+    for a0, iq in outs:
+        starts, nden = edge_window_starts(a0)
+        d["crc_a0"].append(edge_call_crcs(a0))
+        d["crc_iq"].append(edge_call_crcs(iq))
+        d["win_start"].append(starts)
+        d["win_a0"].append(edge_windows(a0, starts))
+        d["win_iq"].append(edge_windows(iq, starts))
+        d["denormal_a0"].append(nden)
+        d["nonfinite"].append(int((~np.isfinite(a0)).sum()))
+        d["peak_a0"].append(np.abs(a0).max())
+    d = {k: np.stack(v) if isinstance(v[0], np.ndarray) else np.array(v) for k, v in d.items()}
+    save_npz(os.path.join(HERE, f"txedge_{name}.npz"), **d, frames=n, kinds=json.dumps(synth.EDGE_AUDIO_KINDS),
+                        audio_crc32=np.array([zlib.crc32(np.ascontiguousarray(r).tobytes()) for r in rows], np.uint32),
+                        args=json.dumps(args))
+    print(f"txedge_{name:14s} denormal a0 {d['denormal_a0'].tolist()}  peak|a0| {[float(f'{p:.4g}') for p in d['peak_a0']]}")
+
+
 def make_cw(name: str):
     args, sig = CW_CONFIGS[name]
     sig = dict(sig)
@@ -433,6 +607,14 @@ def main():
     if a.only in STATUS_CONFIGS:
         make_status(a.only)
         return
+    edge = ([(f"cliprail_{k}", make_clip_rail, k) for k in CLIP_RAIL_CONFIGS]
+            + [(f"rxedge_{k}", make_edge_rx, k) for k in EDGE_CONFIGS]
+            + [(f"txedge_{k}", make_edge_tx, k) for k in EDGE_TX_CONFIGS])
+    if a.only in ("edge", "rxedge", "txedge") or a.only in [e[0] for e in edge]:
+        for full, fn, k in edge:
+            if a.only == "edge" or full == a.only or full.split("_")[0] == a.only:
+                fn(k)
+        return
     make_cmsis()
     paths = subprocess.run([REF, "dump=paths"], check=True, capture_output=True, text=True).stdout
     with open(os.path.join(HERE, "filter_paths.json"), "w") as f:
@@ -459,6 +641,9 @@ def main():
         if a.only and f"tx_{name}" != a.only:
             continue
         make_tx(name)
+    if not a.only:
+        for _, fn, k in edge:
+            fn(k)
 
 
 if __name__ == "__main__":

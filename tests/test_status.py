@@ -103,6 +103,71 @@ def test_device_status_matches_reference(cuda, path):
     assert_bitexact(a1[:, -2048:], g["a1_tail"], "a1 tail")
 
 
+# The clip flags at the rails (cliprail_*.npz, input synth.clip_rail_iq): the reference shifts
+# abs(l) as a signed int32, so a call whose I samples are all -2^31 raises no flag, while
+# -(2^31-1) and 2^31-1 raise all three.
+RAIL_FILES = sorted(glob.glob(os.path.join(HERE, "golden", "cliprail_*.npz")))
+ALL_CLIP = U.ADC_CLIP | U.ADC_HALF_CLIP | U.ADC_QUARTER_CLIP
+
+
+def load_rail_case(path):
+    g = dict(np.load(path, allow_pickle=False))
+    n = int(g["frames"])
+    iq = synth.clip_rail_iq(np.arange(g["clip"].shape[0]), 0, n)
+    assert zlib.crc32(np.ascontiguousarray(iq).tobytes()) == int(g["iq_crc32"]), "synth.clip_rail_iq drifted"
+    # the recorded flags say what the issue is about: nothing at INT32_MIN, everything next to it
+    want = {synth.INT32_MIN: 0, -synth.INT32_MAX: ALL_CLIP, synth.INT32_MAX: ALL_CLIP}
+    for first, value in synth.CLIP_RAIL_STRETCHES:
+        assert (iq[:, first:first + 256, 0] == value).all()
+        assert (g["clip"][:, first // 32:first // 32 + 8] == want[value]).all(), (value, g["clip"])
+    return g, json.loads(str(g["args"])), iq
+
+
+def test_clip_rail_fixture_present():
+    assert len(RAIL_FILES) >= 1
+    for f in RAIL_FILES:
+        load_rail_case(f)
+
+
+@pytest.mark.parametrize("path", RAIL_FILES, ids=lambda p: os.path.basename(p)[9:-4])
+def test_oracle_clip_flags_at_the_rails(path):
+    g, args, iq = load_rail_case(path)
+    C, calls = g["clip"].shape
+    o = oracle.OracleRx(U.build_plan(U.config_from_ref_args(args)), C)
+    clip = np.empty((C, calls), np.int32)
+    for k in range(calls):
+        o.process(np.ascontiguousarray(iq[:, 32 * k:32 * k + 32]))
+        clip[:, k], _ = o.status()
+    np.testing.assert_array_equal(clip, g["clip"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("frames", [32, 256])
+@pytest.mark.parametrize("path", RAIL_FILES, ids=lambda p: os.path.basename(p)[9:-4])
+def test_device_clip_flags_at_the_rails(cuda, back, path, frames):
+    """per 32-frame call, and per launch of 8 calls with the flags OR-ed: a launch that is all
+    -2^31 reports 0"""
+    import torch
+    g, args, iq = load_rail_case(path)
+    C, calls = g["clip"].shape
+    P = frames // 32
+    chain = U.RxChain(U.config_from_ref_args(args), channels=C, frames=frames)
+    clip = torch.zeros(C, dtype=torch.int32, device="cuda")
+    chain.set_clip_output(clip)
+    dev_iq = torch.from_numpy(iq).cuda()
+    got = np.empty((C, calls // P), np.int32)
+    for L in range(calls // P):
+        chain.process(dev_iq[:, L * frames:(L + 1) * frames].contiguous())
+        chain.synchronize()
+        got[:, L] = clip.cpu().numpy()
+        clip.zero_()
+    chain.close()
+    want = np.bitwise_or.reduce(g["clip"].astype(np.int32).reshape(C, calls // P, P), axis=2)
+    np.testing.assert_array_equal(got, want)
+    first = synth.CLIP_RAIL_STRETCHES[0][0] // frames
+    assert (got[:, first:first + 256 // frames] == 0).all()
+
+
 @pytest.mark.gpu
 def test_device_twinpeaks_reset_and_no_auto_iq(cuda):
     """reset() returns every channel to WAIT; without auto I/Q the detector never runs (the

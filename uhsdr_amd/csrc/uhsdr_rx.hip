@@ -194,20 +194,22 @@ __device__ __forceinline__ void twinpeaks_step(float t1, float t3, int& st, int&
 }
 
 // ADC clip indicators of R frames (audio_driver.c:2660-2676): |I| >> IQ_BIT_SHIFT against
-// ADC_CLIP_WARN_THRESHOLD (4096) and its half / quarter, magnitude taken unsigned
+// ADC_CLIP_WARN_THRESHOLD (4096) and its half / quarter.  The level is a signed int32: abs()
+// of -2^31 wraps to -2^31, the arithmetic shift keeps it negative, and so that one sample
+// raises no flag, as in the compiled reference
 template <int R>
 __device__ __forceinline__ unsigned clip_flags(const int4 (&raw)[R / 2])
 {
-    unsigned lv = 0;
+    int lv = -2147483647 - 1;
 #pragma unroll
     for (int j = 0; j < R; ++j)
     {
         const int v = (j & 1) ? raw[j / 2].z : raw[j / 2].x;
-        const unsigned m = (unsigned)(v < 0 ? -(long long)v : (long long)v) >> 16;
+        const int m = (int)(v < 0 ? 0u - (unsigned)v : (unsigned)v) >> 16;
         lv = lv > m ? lv : m;
     }
-    return (lv > 4096u / 4 ? (unsigned)UHSDR_ADC_QUARTER_CLIP : 0u) | (lv > 4096u / 2 ? (unsigned)UHSDR_ADC_HALF_CLIP : 0u) |
-           (lv > 4096u ? (unsigned)UHSDR_ADC_CLIP : 0u);
+    return (lv > 4096 / 4 ? (unsigned)UHSDR_ADC_QUARTER_CLIP : 0u) | (lv > 4096 / 2 ? (unsigned)UHSDR_ADC_HALF_CLIP : 0u) |
+           (lv > 4096 ? (unsigned)UHSDR_ADC_CLIP : 0u);
 }
 
 // R consecutive frames n0.. of one channel: int32 -> f32 x 2^-16 (audio_driver.c:2660-2685),

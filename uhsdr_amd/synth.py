@@ -211,6 +211,111 @@ def tx_audio(channels, start: int, nframes: int, kind: str = "ssb2tone", noise_s
     return _frames(s, s)
 
 
+# Edge inputs: silence, signal / silence / signal (the recursive stages decay through the
+# denormals and sit there until the signal returns), full-scale samples, all 32 bits in use
+EDGE_KINDS = ("zeros", "burst", "impulse", "rails", "lsb", "lowbits")
+EDGE_LEAD, EDGE_GAP = 8192, 196608
+EDGE_FRAMES = EDGE_LEAD + EDGE_GAP + 4096            # 208896 = 102 x 2048
+EDGE_IMPULSE_EVERY = 4099
+EDGE_AUDIO_KINDS = ("zeros", "burst", "rails")
+EDGE_AUDIO_LEAD, EDGE_AUDIO_GAP = 2048, 131072
+EDGE_AUDIO_FRAMES = EDGE_AUDIO_LEAD + EDGE_AUDIO_GAP + 2048   # 135168 = 528 x 256
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def _uniform_int(channels, start, nframes, lo, hi, salt):
+    """integers in [lo, hi] per (channel, sample index, I / Q), counter-based; [C, n, 2] int64"""
+    ch = np.asarray(channels).astype(np.uint64)[:, None, None]
+    idx = np.arange(start, start + nframes, dtype=np.uint64)[None, :, None]
+    iq = np.arange(2, dtype=np.uint64)[None, None, :]
+    key = ((np.uint64(SEED_BASE) + ch) << np.uint64(40)) ^ (np.uint64(salt) << np.uint64(36)) ^ (idx << np.uint64(1)) ^ iq
+    return lo + np.floor(_uniform(key) * (hi - lo + 1)).astype(np.int64)
+
+
+def _rails(n):
+    return np.where((n // 5) % 2 == 0, INT32_MAX, INT32_MIN)
+
+
+def edge_iq(kind: str, channels, start: int, nframes: int, base=None, shift=0, lead: int = EDGE_LEAD,
+            gap: int = EDGE_GAP, **base_kw) -> np.ndarray:
+    """int32 I/Q frames [len(channels), nframes, 2] at the edges of the input range, absolute in
+    `start` like the others.  `base` (ssb_iq by default, am_iq, fm_iq; `base_kw` goes to it) is
+    the signal of the kinds that carry one:
+
+      zeros    silence from the first sample
+      burst    `base` for `lead` frames, zeros for `gap` frames, `base` again; the sample index
+               runs on across the gap.  `shift` (a number, or one per channel) starts the
+               silence that many frames later; it ends at lead + gap all the same
+      impulse  I = INT32_MIN at every 4099th frame, Q = INT32_MAX 2048 frames after each of
+               those; all zero after frame lead + 2 * 4099
+      rails    I alternates between INT32_MAX and INT32_MIN every 5 frames, Q the same 2 frames later
+      lsb      uniform integers in [-3, 3], not shifted up: |x| <= 4.6e-5 after the 2^-16 scaling
+      lowbits  9 x `base` plus uniform integers in [-32768, 32767], clipped to int32: every one
+               of the 32 bits in use, loud enough to wrap the codec frames with the AGC off
+    """
+    channels = np.asarray(channels, dtype=np.int64)
+    base = ssb_iq if base is None else base
+    n = np.arange(start, start + nframes, dtype=np.int64)
+    out = np.zeros((len(channels), nframes, 2), dtype=np.int32)
+    if kind == "zeros":
+        pass
+    elif kind == "burst":
+        sh = np.broadcast_to(np.asarray(shift, dtype=np.int64), channels.shape)
+        quiet = (n[None, :] >= lead + sh[:, None]) & (n[None, :] < lead + gap)
+        out = np.where(quiet[:, :, None], 0, base(channels, start, nframes, **base_kw)).astype(np.int32)
+    elif kind == "impulse":
+        on = n <= lead + 2 * EDGE_IMPULSE_EVERY
+        out[:, on & (n % EDGE_IMPULSE_EVERY == 0), 0] = INT32_MIN
+        out[:, on & (n >= 2048) & ((n - 2048) % EDGE_IMPULSE_EVERY == 0), 1] = INT32_MAX
+    elif kind == "rails":
+        out[:, :, 0] = _rails(n)[None, :]
+        out[:, :, 1] = _rails(n - 2)[None, :]
+    elif kind == "lsb":
+        out = _uniform_int(channels, start, nframes, -3, 3, 1).astype(np.int32)
+    elif kind == "lowbits":
+        loud = base(channels, start, nframes, **base_kw).astype(np.int64) * 9
+        out = np.clip(loud + _uniform_int(channels, start, nframes, -32768, 32767, 2), INT32_MIN, INT32_MAX).astype(np.int32)
+    else:
+        raise ValueError(f"edge_iq: unknown kind {kind!r}")
+    return out
+
+
+def edge_audio(kind: str, channels, start: int, nframes: int, lead: int = EDGE_AUDIO_LEAD,
+               gap: int = EDGE_AUDIO_GAP) -> np.ndarray:
+    """Edge inputs of the transmit chain, codec frames [len(channels), nframes, 2] with the sample
+    in both channels: `zeros`; `burst`, tx_audio for `lead` frames, `gap` frames of silence,
+    tx_audio again; `rails`, INT32_MAX / INT32_MIN alternating every 5 frames."""
+    channels = np.asarray(channels, dtype=np.int64)
+    n = np.arange(start, start + nframes, dtype=np.int64)
+    out = np.zeros((len(channels), nframes, 2), dtype=np.int32)
+    if kind == "zeros":
+        pass
+    elif kind == "burst":
+        quiet = (n >= lead) & (n < lead + gap)
+        out = np.where(quiet[None, :, None], 0, tx_audio(channels, start, nframes)).astype(np.int32)
+    elif kind == "rails":
+        out[:, :, :] = _rails(n)[None, :, None]
+    else:
+        raise ValueError(f"edge_audio: unknown kind {kind!r}")
+    return out
+
+
+CLIP_RAIL_FRAMES = 2048
+# (first frame, I value) of the 256-frame (8-call) stretches of clip_rail_iq
+CLIP_RAIL_STRETCHES = ((256, INT32_MIN), (768, -INT32_MAX), (1280, INT32_MAX))
+
+
+def clip_rail_iq(channels, start: int, nframes: int) -> np.ndarray:
+    """The clip flags at the rails: ssb_iq with I held at INT32_MIN for frames [256, 512), at
+    -(2^31-1) for [768, 1024) and at INT32_MAX for [1280, 1536).  The reference takes abs() of a
+    signed int32, so the first stretch alone raises no flag (audio_driver.c:2662)."""
+    out = ssb_iq(channels, start, nframes)
+    n = np.arange(start, start + nframes)
+    for first, value in CLIP_RAIL_STRETCHES:
+        out[:, (n >= first) & (n < first + 256), 0] = value
+    return out
+
+
 def ssb_iq_torch(c0: int, nch: int, start: int, nframes: int, device, noise_sigma: float = 30.0):
     """Same signal model as ``ssb_iq`` (kind "ssb2tone"), generated on the GPU for large
     benchmark batches: channels c0 .. c0+nch-1.  Tone parameters and noise come from the
