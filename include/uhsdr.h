@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define UHSDR_ABI_VERSION 8
+#define UHSDR_ABI_VERSION 9
 
 typedef enum
 {
@@ -733,8 +733,8 @@ uhsdr_status uhsdr_rx_cw_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_
  *         exactly the bytes UiDriver_TextMsgPutChar receives, '\0', '\a', '\r' and '\n' included
  *         (LTRS and FIGS only switch the table)
  *   total uint32 [C], characters emitted since reset
- * Not built: the RTTY modulator (Rtty_Modulator_GenSample), PSK, and text decoding of either kind
- * in the uhsdr_i2s_* stream. */
+ * Not built: the RTTY modulator (Rtty_Modulator_GenSample), and text decoding of any kind in the
+ * uhsdr_i2s_* stream. */
 typedef struct uhsdr_rtty_s* uhsdr_rtty_handle;
 
 uhsdr_status uhsdr_rtty_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
@@ -753,6 +753,37 @@ uhsdr_status uhsdr_rtty_outputs(uhsdr_rtty_handle h, uint8_t** text, uint32_t** 
 uhsdr_status uhsdr_rtty_synchronize(uhsdr_rtty_handle h);
 uhsdr_status uhsdr_rtty_destroy(uhsdr_rtty_handle h);
 
+/* ---- BPSK decoder: varicode to text, one decoder per channel ----
+ * What the firmware runs on every 12 ksps sample in DEMOD_DIGI with digital_mode BPSK
+ * (Psk_Demodulator_ProcessSample, drivers/audio/psk.c): the band-pass around the 500 Hz carrier,
+ * the mixer and its running sum over one carrier period, the bit decision per symbol and varicode
+ * framing.  Like the firmware it has no carrier or timing recovery.  Exact to the reference: the
+ * same bytes at the same samples.
+ *   speed_idx    0 .. 2: BPSK31, BPSK63, BPSK125
+ *   text_capacity >= 8
+ * Outputs (device memory, or host memory for a host handle), valid once the work enqueued is complete:
+ *   text   uint8 [C][text_capacity], a ring: character k of a channel is at k % text_capacity;
+ *          exactly the bytes UiDriver_TextMsgPutChar receives, '*' for a code that is no character
+ *   total  uint32 [C], characters emitted since reset
+ *   symbol float [C], rx_last_symbol: the averaged phase at the last bit decision, the firmware's
+ *          tuning quantity
+ * Not built: the modulator (Psk_Modulator_GenSample) and QPSK. */
+typedef struct uhsdr_psk_s* uhsdr_psk_handle;
+
+uhsdr_status uhsdr_psk_create(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, void* stream, uhsdr_psk_handle* out);
+/* the same decoder with its state in host memory, for uhsdr_psk_process_host (no device call) */
+uhsdr_status uhsdr_psk_create_host(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, uhsdr_psk_handle* out);
+uhsdr_status uhsdr_psk_reset(uhsdr_psk_handle h);
+uhsdr_status uhsdr_psk_set_stream(uhsdr_psk_handle h, void* stream);
+/* samples: f32 [C][stride], 12 ksps, device memory; decodes n <= stride samples of every channel,
+   stream-ordered */
+uhsdr_status uhsdr_psk_process(uhsdr_psk_handle h, const float* samples, int32_t n, int32_t stride);
+/* the same step function on the CPU over host arrays, for a handle of uhsdr_psk_create_host */
+uhsdr_status uhsdr_psk_process_host(uhsdr_psk_handle h, const float* samples, int32_t n, int32_t stride);
+uhsdr_status uhsdr_psk_outputs(uhsdr_psk_handle h, uint8_t** text, uint32_t** total, float** symbol);
+uhsdr_status uhsdr_psk_synchronize(uhsdr_psk_handle h);
+uhsdr_status uhsdr_psk_destroy(uhsdr_psk_handle h);
+
 /* Digital-mode tap of the RX chain: tap = device f32 [C][N/4], written by every following
    uhsdr_rx_process with a_buffer[0] after biquad_1, the sample the firmware hands its modems
    (audio_driver.c:2537-2557); null turns it off.  Available where the firmware runs them: a 12 ksps
@@ -768,6 +799,11 @@ uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap);
 uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx,
                                     int32_t stopbits_idx, int32_t atc_disable, int32_t text_capacity);
 uhsdr_status uhsdr_rx_rtty_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total);
+/* BPSK text inside the RX chain, as uhsdr_rx_set_rtty_text (arguments as uhsdr_psk_create, outputs
+   as uhsdr_psk_outputs).  The firmware's digital_mode is one value: enabling BPSK text while RTTY
+   text is on, or RTTY text while BPSK text is on, is UHSDR_ARGUMENT_ERROR; turn the other off first. */
+uhsdr_status uhsdr_rx_set_psk_text(uhsdr_rx_handle h, int32_t enable, int32_t speed_idx, int32_t text_capacity);
+uhsdr_status uhsdr_rx_psk_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total, float** symbol);
 
 /* Key beep (AudioManagement_KeyBeep, audio_management.c:368-375 -> the softdds tone added to the
    output at audio_driver.c:2891-2898): the beep's DDS accumulator restarts at 0 and the tone

@@ -4,7 +4,8 @@ measures): C3 (SAM P70 + 1024-point spectrum), C4's per-GPU share (FM-RX P1 and 
 C5's per-GPU share (CW P4 with the CW decoder front end).
 
     python tools/bench_configs.py [--steps K] [--only c3,c4fm,c4tx,c5] > profiles/rNN_configs.jsonl
-    (--only c5rtty: DIGI P48 at the C5 shape without and with the RTTY text decoder in the chain)
+    (--only c5rtty: DIGI P48 at the C5 shape without and with the RTTY text decoder in the chain;
+     --only c5psk: the same without and with the BPSK text decoder)
 
 One JSON line per workload: Msamples/s of 48 kHz frames, ms per call, per-kernel device ms
 (RX: HIP events on the library stream), algorithmic HBM bytes per frame and the fraction of
@@ -58,7 +59,7 @@ FRONT_BLOCK = 0     # --front-block: the RX lines' front outputs per lane (0 = t
 HANDOFF = "persistent"  # --handoff: the pipelined RX lines' front -> back hand-off (uhsdr_rx_set_pipelined 3 / 2 / 1)
 
 
-def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_text=False, rtty_text=False):
+def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_text=False, rtty_text=False, psk_text=False):
     import torch
     import bench
     import uhsdr_amd as U
@@ -77,6 +78,8 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_te
         chain.set_cw_text(True, 0, 64)      # the Morse-to-text decoder on the blocks each call completes
     if rtty_text:
         chain.set_rtty_text(True, 1, 0, 1, False, 64)   # the RTTY decoder on the N/4 tap samples of each call
+    if psk_text:
+        chain.set_psk_text(True, 0, 64)                  # the BPSK decoder on the N/4 tap samples of each call
     join = chain.join if pipelined else None
     ms = time_calls(lambda: chain.process(iq, audio, None), steps, warmup, join)
     chain.enable_timing(True)
@@ -98,6 +101,9 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_te
     if rtty_text:
         out["rtty_text"] = True
         out["rtty_text_chars"] = int(chain.rtty_text_outputs.read()[1].sum())
+    if psk_text:
+        out["psk_text"] = True
+        out["psk_text_chars"] = int(chain.psk_text_outputs.read()[1].sum())
     chain.close()
     if out["handoff_timeouts"]:
         raise RuntimeError(f"{name}: a device hand-off poll gave up: the line is invalid")
@@ -217,6 +223,15 @@ def main():
         for on in (False, True):
             lines.append(rx_line("C5 shape: DIGI P48" + (" + digital-mode tap + RTTY text (rtty_decode)" if on else ""),
                                  cfg, C, N, tiled(gen, C, N), a.steps, a.warmup, rtty_text=on))
+    if "c5psk" in want:
+        # DIGI P48 at the C5 batch shape, BPSK31 looping a message: text off, then on
+        import functools
+        C, N = 1048576 // 8, 256
+        cfg = U.default_config(filter_path=48, dmod_mode=U.DEMOD_DIGI)
+        gen = functools.partial(synth.psk_iq, text="CQ de UHSDR k ")
+        for on in (False, True):
+            lines.append(rx_line("C5 shape: DIGI P48" + (" + digital-mode tap + BPSK text (psk_decode)" if on else ""),
+                                 cfg, C, N, tiled(gen, C, N), a.steps, a.warmup, psk_text=on))
     if "c5fir" in want:
         import numpy as np
         C, N = 1048576 // 8, 256

@@ -23,3 +23,4 @@ from .i2s import Transceiver  # noqa: F401
 from .fir import FirBatch  # noqa: F401
 from .cwdec import CwDecoder  # noqa: F401
 from .rtty import RttyDecoder  # noqa: F401
+from .psk import PskDecoder  # noqa: F401

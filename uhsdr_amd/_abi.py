@@ -18,7 +18,7 @@ MAX_INTERP = 16
 IQ_BLOCK_SIZE = 32
 FILTER_PATH_NUM = 87
 
-ABI_VERSION = 8  # include/uhsdr.h UHSDR_ABI_VERSION: checked against the library at load()
+ABI_VERSION = 9  # include/uhsdr.h UHSDR_ABI_VERSION: checked against the library at load()
 UHSDR_OK = 0
 UHSDR_ARGUMENT_ERROR = -1
 UHSDR_LENGTH_ERROR = -2
@@ -271,6 +271,17 @@ SIGNATURES = {
     "uhsdr_rx_set_digi_tap": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_rx_set_rtty_text": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "uhsdr_rx_rtty_text_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "uhsdr_psk_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_psk_create_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "uhsdr_psk_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_psk_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_psk_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_psk_process_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_psk_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "uhsdr_psk_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_psk_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_rx_set_psk_text": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "uhsdr_rx_psk_text_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
 }
 
 _lib = None

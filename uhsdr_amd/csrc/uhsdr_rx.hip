@@ -3472,7 +3472,8 @@ struct uhsdr_rx_s
     uint8_t* cwt_signal;     // its input [C][N/32] when the user set no signal buffer
     float* tap;              // user's digital-mode tap [C][Nd] (uhsdr_rx_set_digi_tap), or null
     uhsdr_rtty_handle rtty;  // RTTY text decoder (uhsdr_rx_set_rtty_text), null when off
-    float* rtty_tap;         // its input [C][Nd] when the user set no tap
+    uhsdr_psk_handle psk;    // BPSK text decoder (uhsdr_rx_set_psk_text), null when off; never both
+    float* text_tap;         // the decoder's input [C][Nd] when the user set no tap
     long long calls_done;
     long long front_launches; // oscillator ping-pong parity
     // pipelined mode (uhsdr_rx_set_pipelined): rx_back on a side stream, decimated hand-off
@@ -3859,6 +3860,13 @@ extern "C" uhsdr_status uhsdr_rx_reset(uhsdr_rx_handle h)
         const uhsdr_status cr = uhsdr_rtty_reset(h->rtty);
         if (cr != UHSDR_OK) return cr;
     }
+    if (h->psk)
+    {
+        const uhsdr_status cs = uhsdr_psk_set_stream(h->psk, h->stream);
+        if (cs != UHSDR_OK) return cs;
+        const uhsdr_status cr = uhsdr_psk_reset(h->psk);
+        if (cr != UHSDR_OK) return cr;
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->dec_samples = 0;
     h->calls_done = 0;
@@ -4111,7 +4119,7 @@ extern "C" uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap)
         if (ts != UHSDR_OK) return ts;
     }
     float* own = nullptr;
-    if (!tap && h->rtty && !h->rtty_tap)
+    if (!tap && (h->rtty || h->psk) && !h->text_tap)
     {
         // the text decoder goes on reading a row: the handle's own
         if (hipMalloc((void**)&own, sizeof(float) * (size_t)h->C * h->Nd) != hipSuccess)
@@ -4121,13 +4129,13 @@ extern "C" uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap)
         }
     }
     HIPCHK(sync_all(h));
-    if (own) h->rtty_tap = own;
+    if (own) h->text_tap = own;
     h->tap = tap;
     return UHSDR_OK;
 }
 
 // the row the TAP kernel instances write, or null: the launch runs the instances without a tap
-static float* tap_row(const uhsdr_rx_s* h) { return h->tap ? h->tap : h->rtty ? h->rtty_tap : nullptr; }
+static float* tap_row(const uhsdr_rx_s* h) { return h->tap ? h->tap : (h->rtty || h->psk) ? h->text_tap : nullptr; }
 
 // RTTY text (uhsdr_rtty.hip) on the tap row of every call
 extern "C" uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx,
@@ -4142,6 +4150,8 @@ extern "C" uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable
     }
     const uhsdr_status ts = tap_supported(h, "rtty text");
     if (ts != UHSDR_OK) return ts;
+    // the firmware's digital_mode is one value
+    if (enable && h->psk) { uhsdr_set_error("rtty text: psk text is on (uhsdr_rx_set_psk_text), turn it off first"); return UHSDR_ARGUMENT_ERROR; }
     uhsdr_rtty_handle dec = nullptr;
     float* row = nullptr;
     if (enable)
@@ -4159,9 +4169,12 @@ extern "C" uhsdr_status uhsdr_rx_set_rtty_text(uhsdr_rx_handle h, int32_t enable
     }
     HIPCHK(sync_all(h));
     if (h->rtty) (void)uhsdr_rtty_destroy(h->rtty);
-    if (h->rtty_tap) (void)hipFree(h->rtty_tap);
+    if (!h->psk)
+    {
+        if (h->text_tap) (void)hipFree(h->text_tap);
+        h->text_tap = row;
+    }
     h->rtty = dec;
-    h->rtty_tap = row;
     return UHSDR_OK;
 }
 
@@ -4178,6 +4191,60 @@ static uhsdr_status launch_rtty_text(uhsdr_rx_s* h, hipStream_t st)
     const uhsdr_status ss = uhsdr_rtty_set_stream(h->rtty, st);
     if (ss != UHSDR_OK) return ss;
     return uhsdr_rtty_process(h->rtty, tap_row(h), h->Nd, h->Nd);
+}
+
+// BPSK text (uhsdr_psk.hip) on the tap row of every call
+extern "C" uhsdr_status uhsdr_rx_set_psk_text(uhsdr_rx_handle h, int32_t enable, int32_t speed_idx, int32_t text_capacity)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    // the firmware decodes PSK only in DEMOD_DIGI (is_demod_psk, audio_driver.c:2547)
+    if (h->plan.dmod_mode != UHSDR_DEMOD_DIGI)
+    {
+        uhsdr_set_error("psk text: needs demodulator mode DIGI, not mode %d", (int)h->plan.dmod_mode);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    const uhsdr_status ts = tap_supported(h, "psk text");
+    if (ts != UHSDR_OK) return ts;
+    // the firmware's digital_mode is one value
+    if (enable && h->rtty) { uhsdr_set_error("psk text: rtty text is on (uhsdr_rx_set_rtty_text), turn it off first"); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_psk_handle dec = nullptr;
+    float* row = nullptr;
+    if (enable)
+    {
+        // (argument errors before anything changes)
+        const uhsdr_status st = uhsdr_psk_create(h->C, speed_idx, text_capacity, h->stream, &dec);
+        if (st != UHSDR_OK) return st;
+        if (!h->tap && hipMalloc((void**)&row, sizeof(float) * (size_t)h->C * h->Nd) != hipSuccess)
+        {
+            uhsdr_set_error("psk text: device allocation failed");
+            (void)uhsdr_psk_destroy(dec);
+            return UHSDR_DEVICE_ERROR;
+        }
+    }
+    HIPCHK(sync_all(h));
+    if (h->psk) (void)uhsdr_psk_destroy(h->psk);
+    if (!h->rtty)
+    {
+        if (h->text_tap) (void)hipFree(h->text_tap);
+        h->text_tap = row;
+    }
+    h->psk = dec;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_psk_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_t** total, float** symbol)
+{
+    if (!h || !h->psk) { uhsdr_set_error("psk text is off (uhsdr_rx_set_psk_text)"); return UHSDR_ARGUMENT_ERROR; }
+    return uhsdr_psk_outputs(h->psk, text, total, symbol);
+}
+
+// the call's Nd tap samples through the BPSK decoder, after the kernel that wrote them and on its stream
+static uhsdr_status launch_psk_text(uhsdr_rx_s* h, hipStream_t st)
+{
+    if (!h->psk) return UHSDR_OK;
+    const uhsdr_status ss = uhsdr_psk_set_stream(h->psk, st);
+    if (ss != UHSDR_OK) return ss;
+    return uhsdr_psk_process(h->psk, tap_row(h), h->Nd, h->Nd);
 }
 
 extern "C" uhsdr_status uhsdr_rx_set_clip_output(uhsdr_rx_handle h, uint32_t* clip)
@@ -4671,6 +4738,7 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
         RXSTEP(chain_call(h, iq, audio, audio0, dst, fma));
         RXSTEP(launch_cw_text(h, cw0, h->stream));
         RXSTEP(launch_rtty_text(h, h->stream));
+        RXSTEP(launch_psk_text(h, h->stream));
     }
     else
     {
@@ -4687,6 +4755,7 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
         RXSTEP(launch_back(h, r, bk, launch));
         RXSTEP(launch_cw_text(h, cw0, back_stream(h)));
         RXSTEP(launch_rtty_text(h, back_stream(h)));
+        RXSTEP(launch_psk_text(h, back_stream(h)));
         if (h->pipelined) h->pipe_calls += 1;
         if (r.side) h->side_dirty = 1;
         h->main_back = !r.side;
@@ -4963,7 +5032,8 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
     if (h->cwt) (void)uhsdr_cwdec_destroy(h->cwt);
     if (h->cwt_signal) (void)hipFree(h->cwt_signal);
     if (h->rtty) (void)uhsdr_rtty_destroy(h->rtty);
-    if (h->rtty_tap) (void)hipFree(h->rtty_tap);
+    if (h->psk) (void)uhsdr_psk_destroy(h->psk);
+    if (h->text_tap) (void)hipFree(h->text_tap);
     if (h->side)
     {
         (void)hipEventDestroy(h->ev_front);

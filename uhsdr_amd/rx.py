@@ -52,6 +52,8 @@ class RxChain:
             self._cw_text.seen[:] = 0
         if getattr(self, "_rtty_text", None) is not None:
             self._rtty_text.seen[:] = 0
+        if getattr(self, "_psk_text", None) is not None:
+            self._psk_text.seen[:] = 0
 
     def _shape_ok(self, t, last):
         shp = tuple(t.shape)
@@ -187,6 +189,31 @@ class RxChain:
     @property
     def rtty_text_outputs(self):
         return getattr(self, "_rtty_text", None)
+
+    def set_psk_text(self, enable: bool = True, speed: int = 0, text_capacity: int = 64) -> None:
+        """BPSK decoding of the tap samples of every following call (uhsdr_rx_set_psk_text): only in
+        dmod_mode DIGI on a 12 ksps path, and not while RTTY text is on.  speed as uhsdr_amd.psk."""
+        _abi.check(self.lib.uhsdr_rx_set_psk_text(self.handle, int(bool(enable)), int(speed), int(text_capacity)),
+                   "uhsdr_rx_set_psk_text")
+        self._psk_text = None
+        if enable:
+            from .psk import PskOutputs
+            p = [C.c_void_p() for _ in range(3)]
+            _abi.check(self.lib.uhsdr_rx_psk_text_outputs(self.handle, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])),
+                       "uhsdr_rx_psk_text_outputs")
+            self._psk_text = PskOutputs(self.lib, self.channels, int(text_capacity), True, *(x.value for x in p))
+
+    def psk_text(self):
+        """Per channel, the bytes decoded since the last read (synchronises).  With
+        .psk_text_outputs.read() the text ring and the totals are available as arrays."""
+        if getattr(self, "_psk_text", None) is None:
+            raise RuntimeError("psk text is off: set_psk_text() first")
+        self.synchronize()
+        return self._psk_text.new_text()
+
+    @property
+    def psk_text_outputs(self):
+        return getattr(self, "_psk_text", None)
 
     @property
     def cw_blocks_max(self) -> int:

@@ -568,3 +568,132 @@ def rtty_chain_fixture(path: str) -> dict:
     g["iq"] = iq
     g["config"] = (int(g["shift_idx"]), int(g["speed_idx"]), int(g["stopbits_idx"]), int(g["atc_disable"]))
     return g
+
+
+# G3PLX varicode as the BPSK decoder reads it: byte -> code, sent highest bit first and followed by
+# two 0 bits; a 0 bit is a phase reversal, a 1 bit none.  Codes start and end with a 1 and hold no
+# two 0 bits in a row; bytes 128 .. 255 take the valid codes the ASCII half leaves unused, in order.
+_VARICODE_ASCII = (
+    "2AB 2DB 2ED 377 2EB 35F 2EF 2FD 2FF 0EF 01D 36F 2DD 01F 375 3AB 2F7 2F5 3AD 3AF 35B 36B 36D 357 37B 37D 3B7 355 35D 3BB 2FB 37F "
+    "001 1FF 15F 1F5 1DB 2D5 2BB 17F 0FB 0F7 16F 1DF 075 035 057 1AF 0B7 0BD 0ED 0FF 177 15B 16B 1AD 1AB 1B7 0F5 1BD 1ED 055 1D7 2AF "
+    "2BD 07D 0EB 0AD 0B5 077 0DB 0FD 155 07F 1FD 17D 0D7 0BB 0DD 0AB 0D5 1DD 0AF 06F 06D 157 1B5 15D 175 17B 2AD 1F7 1EF 1FB 2BF 16D "
+    "2DF 00B 05F 02F 02D 003 03D 05B 02B 00D 1EB 0BF 01B 03B 00F 007 03F 1BF 015 017 005 037 07B 06B 0DF 05D 1D5 2B7 1BB 2B5 2D7 3B5")
+PSK_SPEEDS = (31.25, 62.5, 125.0)                            # speed_idx 0 .. 2
+PSK_CARRIER = 500.0
+
+
+def varicode_table():
+    """code of every byte 0 .. 255"""
+    codes = [int(x, 16) for x in _VARICODE_ASCII.split()]
+    used, c = set(codes), 0
+    while len(codes) < 256:
+        c += 1
+        b = bin(c)[2:]
+        if b[-1] == "1" and "00" not in b and c not in used:
+            codes.append(c)
+    return codes
+
+
+def varicode_bits(data, preamble: int = 8, idle_ones: int = 0, postamble: int = 8) -> np.ndarray:
+    """The bit stream that sends `data` (bytes or a latin-1 string): `preamble` 0 bits (reversals,
+    the idle of a BPSK transmitter), `idle_ones` 1 bits (steady carrier), every byte's code followed
+    by two 0 bits, `postamble` 0 bits."""
+    if isinstance(data, str):
+        data = data.encode("latin-1")
+    table = varicode_table()
+    bits = [0] * preamble + [1] * idle_ones
+    for byte in data:
+        bits += [int(b) for b in bin(table[byte])[2:]] + [0, 0]
+    return np.array(bits + [0] * postamble, np.uint8)
+
+
+def _psk_baseband(bits, per_bit: int, first: float = 1.0) -> np.ndarray:
+    """The envelope between -1 and 1, len(bits) * per_bit samples from the centre of the bit before
+    the first: constant through a 1 bit, half a cosine from one polarity to the other through a 0
+    bit (a raised-cosine reversal, centre to centre)."""
+    pol = first * np.cumprod(np.concatenate([[1.0], np.where(np.asarray(bits) != 0, 1.0, -1.0)]))
+    a, b = np.repeat(pol[:-1], per_bit), np.repeat(pol[1:], per_bit)
+    frac = np.tile(np.arange(per_bit) / per_bit, len(bits))
+    return 0.5 * (a + b) + 0.5 * (a - b) * np.cos(np.pi * frac)
+
+
+def psk_audio(text, baud: float = 31.25, amplitude: float = 1000.0, offset: int = 0, noise_sigma: float = 0.0, df: float = 0.0,
+              seed: int = 0, preamble: int = 8, idle_ones: int = 0, postamble: int = 8, lead: int = 0, silence: int = 0,
+              repeat: int = 1, rate: float = 12000.0) -> np.ndarray:
+    """12 ksps float32 audio of a BPSK transmission, the decoder's stand-alone input: a carrier at
+    500 Hz + `df` whose polarity follows varicode_bits(text, preamble, idle_ones, postamble) with
+    raised-cosine reversals, after `lead` samples of steady carrier.  `noise_sigma` adds white noise
+    (counter-based, `seed`); the first `offset` samples are dropped, which moves the bit boundaries
+    against the decoder's fixed symbol clock and lets a stream start mid-character.  `silence`
+    samples of exact zero follow, and the whole is sent `repeat` times.
+    Samples are not rounded: amplitudes from 1e-28 to 1e34 are meaningful inputs."""
+    per_bit = int(round(rate / baud))
+    m = np.concatenate([np.ones(lead), _psk_baseband(varicode_bits(text, preamble, idle_ones, postamble), per_bit)])
+    s = amplitude * m * np.sin(2.0 * np.pi * (PSK_CARRIER + df) / rate * np.arange(len(m)))
+    if noise_sigma > 0:
+        s = s + _noise(np.array([2 << 16 | seed], np.int64), 0, len(m), noise_sigma)[0][0]
+    with np.errstate(over="ignore"):
+        return np.tile(np.concatenate([s[offset:], np.zeros(silence)]), repeat).astype(np.float32)
+
+
+def psk_iq(channels, start: int, nframes: int, text: str, baud: float = 31.25, noise_sigma: float = 30.0, carrier: float = 12000.0,
+           amplitude: float = 1500.0, lead: int = 24000, df: float = 0.0, preamble: int = 16):
+    """48 ksps I/Q of a BPSK signal on the upper side of `carrier`, at +500 Hz + `df`: steady carrier
+    for `lead` frames plus a per-channel start offset of up to one second, then `preamble` reversals
+    and `text`, repeated for ever; plus noise.  The BPSK text decoder's input through the RX chain
+    (DEMOD_DIGI)."""
+    channels = np.asarray(channels, dtype=np.int64)
+    ch = channels.astype(np.uint64)
+    base = (np.uint64(SEED_BASE) + ch) << np.uint64(20)
+    delay = lead + np.floor(FS * _uniform(base + np.uint64(16))).astype(np.int64)
+    ph_c = 2.0 * np.pi * _uniform(base + np.uint64(17))
+    bits = varicode_bits(text, preamble, 0, 0)
+    env = _psk_baseband(np.concatenate([bits, bits]), int(round(FS / baud)))      # two passes: an even number of reversals
+    n = np.arange(start, start + nframes, dtype=np.int64)
+    i_sig = np.empty((len(channels), nframes))
+    q_sig = np.empty((len(channels), nframes))
+    for k in range(len(channels)):
+        rel = n - int(delay[k])
+        m = np.where(rel >= 0, env[np.where(rel >= 0, rel, 0) % len(env)], 1.0)
+        ph = 2.0 * np.pi / FS * (carrier + PSK_CARRIER + df) * n.astype(np.float64) + ph_c[k]
+        i_sig[k], q_sig[k] = amplitude * m * np.cos(ph), amplitude * m * np.sin(ph)
+    if noise_sigma > 0:
+        ni, nq = _noise(channels, start, nframes, noise_sigma)
+        i_sig, q_sig = i_sig + ni, q_sig + nq
+    return _frames(i_sig, q_sig)
+
+
+def psk_fixture(path: str) -> dict:
+    """A recorded stand-alone BPSK case (an npz of tools/psk/make_psk_golden.py) with its input
+    regenerated from the recorded arguments and checked against the recorded crc32: the file's
+    arrays plus `audio` (float32, read-only), `sent` (bytes) and `speed` (speed_idx)."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    g["sent"] = bytes(g["message"])
+    audio = psk_audio(g["sent"], **json.loads(str(g["gen"])))
+    if len(audio) != int(g["samples"]) or zlib.crc32(audio.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    audio.setflags(write=False)
+    g["audio"] = audio
+    g["speed"] = int(g["speed_idx"])
+    return g
+
+
+def psk_chain_fixture(path: str) -> dict:
+    """A recorded BPSK case through the receive chain (psk_chain_*.npz): the file's arrays plus `iq`
+    (int32 [frames][2], one channel, read-only) regenerated from the recorded arguments of psk_iq
+    and checked against the recorded crc32, and `speed`."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    gen = json.loads(str(g["gen"]))
+    iq = np.ascontiguousarray(psk_iq([gen.pop("channel")], 0, gen.pop("nframes"), gen.pop("text"), **gen)[0], dtype=np.int32)
+    if zlib.crc32(iq.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    iq.setflags(write=False)
+    g["iq"] = iq
+    g["speed"] = int(g["speed_idx"])
+    return g
