@@ -433,7 +433,7 @@ enum { UHSDR_TX_AUDIO_MIC = 0, UHSDR_TX_AUDIO_LINEIN_L = 1, UHSDR_TX_AUDIO_LINEI
 
 typedef struct uhsdr_tx_config
 {
-    int32_t dmod_mode;            /* ts.dmod_mode: UHSDR_DEMOD_USB, _LSB, _AM or _FM */
+    int32_t dmod_mode;            /* ts.dmod_mode: UHSDR_DEMOD_USB, _LSB, _AM, _FM or _DIGI (uhsdr_tx_set_rtty_mod) */
     int32_t iq_freq_mode;         /* ts.iq_freq_mode */
     int32_t audio_source;         /* ts.tx_audio_source: MIC, LINEIN_L, LINEIN_R, DIG, DIGIQ */
     int32_t mic_gain_mult;        /* ts.tx_mic_gain_mult (codec.c:313-321) */
@@ -452,7 +452,8 @@ typedef struct uhsdr_tx_config
     int32_t fm_subaudible_tone;   /* ts.fm_subaudible_tone_gen_select: index into fm_subaudible_tone_table, 0 = off */
     int32_t fm_tone_burst_mode;   /* ts.fm_tone_burst_mode: 0 off, 1 1750 Hz, 2 2135 Hz (fm_tone_burst_freq,
                                      audio_management.c:328), sent while uhsdr_tx_set_tone_burst is on */
-    int32_t reserved[13];
+    int32_t digi_lsb;             /* ts.digi_lsb: UHSDR_DEMOD_DIGI transmits on the lower sideband */
+    int32_t reserved[12];
 } uhsdr_tx_config;
 
 typedef struct uhsdr_tx_plan
@@ -541,6 +542,32 @@ uhsdr_status uhsdr_tx_set_tune(uhsdr_tx_handle h, int32_t tune);
    the fm_tone_burst_mode tone replaces the sub-audible tone in the FM modulator.  No effect for
    SSB or with fm_tone_burst_mode 0. */
 uhsdr_status uhsdr_tx_set_tone_burst(uhsdr_tx_handle h, int32_t active);
+/* DIGI transmit (dmod_mode UHSDR_DEMOD_DIGI; ts.dvmode with digital_mode RTTY or BPSK,
+   tx_processor.c:973-983): the handle owns one modulator (uhsdr_rttymod_* / uhsdr_pskmod_* below,
+   arguments as their create) and an int16 row [C][N].  With a modulator on, uhsdr_tx_process
+   ignores `audio` (may be null) and runs TxProcessor_Rtty / TxProcessor_Psk (:811-845): N modulator
+   samples per channel, the TX lattice (TxProcessor_FilterAudio(true, false): no bass / treble
+   biquads, no input gain, no ALC), TxProcessor_SSB(..., 0, ts.digi_lsb): the Hilbert pair, swapped
+   for digi_lsb, and no frequency translation whatever iq_freq_mode says, then the final stage with
+   iq_gain_comp SSB_GAIN_COMP (RTTY) or 1.0 (BPSK).  a0 is a_buffer[0] after the lattice.  The
+   transmitter is at zero IF in these modes (radio_management.c:587-605), so gain_i, gain_q and
+   phase_balance of the config are the firmware's IQ_TRANS_OFF values.  The modulator kernel runs
+   first on the handle's stream, the lattice in a kernel of its own that reads the row; tx_iq,
+   pipelined mode and the FMA precision work as for SSB.
+   One modulator at a time: enabling one while the other is on is UHSDR_ARGUMENT_ERROR, as are all
+   five calls on a handle of another mode.  A DIGI handle without a modulator refuses
+   uhsdr_tx_process, and uhsdr_tx_set_tune is refused on a DIGI handle (the firmware's dvmode branch
+   never looks at ts.tune); the USB I/Q source is refused for DIGI at create.  uhsdr_tx_reset resets
+   the modulator (queues emptied, StartTX / PrepareTx); uhsdr_tx_prepare_run does not touch it.
+   mod_put_text, mod_start (StartTX / PrepareTx) and mod_outputs are the modulator's put_text,
+   start_tx / prepare_tx and outputs.  Not built: the keyer as text entry
+   (TxProcessor_CwInputForDigitalModes with a keyer mode other than STRAIGHT) and the OVI40 sidetone. */
+uhsdr_status uhsdr_tx_set_rtty_mod(uhsdr_tx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                                   int32_t text_capacity);
+uhsdr_status uhsdr_tx_set_psk_mod(uhsdr_tx_handle h, int32_t enable, int32_t speed_idx, int32_t text_capacity);
+uhsdr_status uhsdr_tx_mod_put_text(uhsdr_tx_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted);
+uhsdr_status uhsdr_tx_mod_start(uhsdr_tx_handle h);
+uhsdr_status uhsdr_tx_mod_outputs(uhsdr_tx_handle h, uint32_t** consumed, uint32_t** txoff_at, uint8_t** state);
 int32_t      uhsdr_sizeof_tx_config(void);
 int32_t      uhsdr_sizeof_tx_plan(void);
 
@@ -733,8 +760,8 @@ uhsdr_status uhsdr_rx_cw_text_outputs(uhsdr_rx_handle h, uint8_t** text, uint32_
  *         exactly the bytes UiDriver_TextMsgPutChar receives, '\0', '\a', '\r' and '\n' included
  *         (LTRS and FIGS only switch the table)
  *   total uint32 [C], characters emitted since reset
- * Not built: the RTTY modulator (Rtty_Modulator_GenSample), and text decoding of any kind in the
- * uhsdr_i2s_* stream. */
+ * The RTTY modulator (Rtty_Modulator_GenSample) is uhsdr_rttymod_* below.
+ * Not built: text decoding of any kind in the uhsdr_i2s_* stream. */
 typedef struct uhsdr_rtty_s* uhsdr_rtty_handle;
 
 uhsdr_status uhsdr_rtty_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
@@ -767,7 +794,8 @@ uhsdr_status uhsdr_rtty_destroy(uhsdr_rtty_handle h);
  *   total  uint32 [C], characters emitted since reset
  *   symbol float [C], rx_last_symbol: the averaged phase at the last bit decision, the firmware's
  *          tuning quantity
- * Not built: the modulator (Psk_Modulator_GenSample) and QPSK. */
+ * The modulator (Psk_Modulator_GenSample) is uhsdr_pskmod_* below.
+ * Not built: QPSK. */
 typedef struct uhsdr_psk_s* uhsdr_psk_handle;
 
 uhsdr_status uhsdr_psk_create(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, void* stream, uhsdr_psk_handle* out);
@@ -783,6 +811,73 @@ uhsdr_status uhsdr_psk_process_host(uhsdr_psk_handle h, const float* samples, in
 uhsdr_status uhsdr_psk_outputs(uhsdr_psk_handle h, uint8_t** text, uint32_t** total, float** symbol);
 uhsdr_status uhsdr_psk_synchronize(uhsdr_psk_handle h);
 uhsdr_status uhsdr_psk_destroy(uhsdr_psk_handle h);
+
+/* ---- RTTY and BPSK modulators: text to 48 ksps audio, one modulator per channel ----
+ * What the firmware's transmit path generates per sample in DEMOD_DIGI: Rtty_Modulator_GenSample
+ * (drivers/audio/rtty.c: Baudot framing with LTRS / FIGS only at a change of set, idle LTRS, two
+ * softdds tones with the phase-continuous change between them) and Psk_Modulator_GenSample
+ * (drivers/audio/psk.c: preamble, varicode, the raised envelope at phase reversals, postamble after
+ * EOT).  Exact to the reference: the same int16 at every sample.  Pure integer arithmetic.
+ *   rttymod: shift_idx, speed_idx, stopbits_idx as uhsdr_rtty_create (space = 915 Hz + shift, mark =
+ *            915 Hz; 1.5 and 2 stop bits both send two)
+ *   pskmod:  speed_idx as uhsdr_psk_create
+ *   text_capacity >= 8: the size of a channel's text queue, which models the firmware's ring
+ *            (uhsdr_digi_buffer.c).  One slot stays free: text_capacity - 1 characters fit.
+ * create and reset leave a modulator as a fresh firmware leaves it after the modem's init and
+ * Rtty_Modulator_StartTX / Psk_Modulator_PrepareTx, with an empty queue: RTTY idles on LTRS, BPSK
+ * starts its preamble.  start_tx / prepare_tx are these two calls alone, on every channel,
+ * stream-ordered; they keep the queue and what the firmware's calls keep.
+ * put_text: text = host uint8 [C][stride], len = host int32 [C] with 0 <= len[c] <= stride.  Appends to
+ * every channel's queue what fits of its len[c] bytes and reports that count in accepted [C] (host,
+ * may be null).  It is ordered after the work already enqueued: on a device handle it synchronises
+ * the handle's stream to learn how much each modulator has taken, and returns with the text in place.
+ * Byte 0x04 (EOT) requests TX-off: RTTY in the sample that takes it, going on with the text behind
+ * it; BPSK after its postamble, where the modulator turns OFF and stays silent until prepare_tx.
+ * process: audio = int16 [C][stride], device memory (host memory for process_host); writes n <= stride
+ * samples of every channel, stream-ordered.
+ * Outputs (device memory, or host memory for a host handle), valid once the work enqueued is complete:
+ *   consumed uint32 [C], characters taken from the queue since reset (what the firmware echoes to
+ *            UiDriver_TextMsgPutChar)
+ *   txoff_at uint32 [C], the index since reset of the first sample in which the channel requested
+ *            TX-off (RadioManagement_Request_TxOff), 0xffffffff if none.  The index is 32 bits wide:
+ *            it wraps after 2^32 samples, 24.9 hours at 48 ksps, and a request in sample
+ *            0xffffffff reads as none; reset before that where txoff_at matters
+ *   state    uint8 [C], BPSK: 0 OFF, 1 PREAMBLE, 2 ACTIVE, 3 POSTAMBLE, 4 INACTIVE; RTTY: 0
+ * set_stream waits for the work enqueued on the stream the handle held, so the new stream's work
+ * and put_text are ordered after it.
+ * Inside the transmit chain (TxProcessor_Rtty / TxProcessor_Psk): uhsdr_tx_set_rtty_mod /
+ * uhsdr_tx_set_psk_mod above.
+ * Not built: a QPSK modulator (the firmware has none), the firmware's consumer tag on the ring, the
+ * CW generator / keyer as a text source, FreeDV. */
+typedef struct uhsdr_rttymod_s* uhsdr_rttymod_handle;
+typedef struct uhsdr_pskmod_s* uhsdr_pskmod_handle;
+
+uhsdr_status uhsdr_rttymod_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                                  int32_t text_capacity, void* stream, uhsdr_rttymod_handle* out);
+/* the same modulator with its state in host memory, for uhsdr_rttymod_process_host (no device call) */
+uhsdr_status uhsdr_rttymod_create_host(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                                       int32_t text_capacity, uhsdr_rttymod_handle* out);
+uhsdr_status uhsdr_rttymod_reset(uhsdr_rttymod_handle h);
+uhsdr_status uhsdr_rttymod_start_tx(uhsdr_rttymod_handle h);
+uhsdr_status uhsdr_rttymod_put_text(uhsdr_rttymod_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted);
+uhsdr_status uhsdr_rttymod_process(uhsdr_rttymod_handle h, int16_t* audio, int32_t n, int32_t stride);
+uhsdr_status uhsdr_rttymod_process_host(uhsdr_rttymod_handle h, int16_t* audio, int32_t n, int32_t stride);
+uhsdr_status uhsdr_rttymod_outputs(uhsdr_rttymod_handle h, uint32_t** consumed, uint32_t** txoff_at, uint8_t** state);
+uhsdr_status uhsdr_rttymod_set_stream(uhsdr_rttymod_handle h, void* stream);
+uhsdr_status uhsdr_rttymod_synchronize(uhsdr_rttymod_handle h);
+uhsdr_status uhsdr_rttymod_destroy(uhsdr_rttymod_handle h);
+
+uhsdr_status uhsdr_pskmod_create(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, void* stream, uhsdr_pskmod_handle* out);
+uhsdr_status uhsdr_pskmod_create_host(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, uhsdr_pskmod_handle* out);
+uhsdr_status uhsdr_pskmod_reset(uhsdr_pskmod_handle h);
+uhsdr_status uhsdr_pskmod_prepare_tx(uhsdr_pskmod_handle h);
+uhsdr_status uhsdr_pskmod_put_text(uhsdr_pskmod_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted);
+uhsdr_status uhsdr_pskmod_process(uhsdr_pskmod_handle h, int16_t* audio, int32_t n, int32_t stride);
+uhsdr_status uhsdr_pskmod_process_host(uhsdr_pskmod_handle h, int16_t* audio, int32_t n, int32_t stride);
+uhsdr_status uhsdr_pskmod_outputs(uhsdr_pskmod_handle h, uint32_t** consumed, uint32_t** txoff_at, uint8_t** state);
+uhsdr_status uhsdr_pskmod_set_stream(uhsdr_pskmod_handle h, void* stream);
+uhsdr_status uhsdr_pskmod_synchronize(uhsdr_pskmod_handle h);
+uhsdr_status uhsdr_pskmod_destroy(uhsdr_pskmod_handle h);
 
 /* Digital-mode tap of the RX chain: tap = device f32 [C][N/4], written by every following
    uhsdr_rx_process with a_buffer[0] after biquad_1, the sample the firmware hands its modems

@@ -206,6 +206,34 @@ def main():
                       "hbm_frac": round(C * N * per / ms / 1e6 / HBM_PEAK_GBS, 4),
                       "finite": bool(torch.isfinite(a0).all().item()) and bool((iq != 0).any().item())})
         tx.close()
+    if "c4txdigi" in want:
+        # DIGI transmit at the C4 SSB-TX shape: the modulator kernel, the lattice alone (tx_voice_digi),
+        # tx_iq without translation; texts in rotation, every fourth queue empty.  Beside the SSB-TX
+        # line of the same process when both are asked for (--only c4tx,c4txdigi)
+        C, N = 262144 // 8, 256
+        s = torch.cuda.current_stream()
+        texts = [b"RYRY CQ DE UHSDR K", b"the quick brown fox 0123456789", b"CQ CQ de UHSDR, Pse k #7", b""]
+        for kind in ("rtty", "psk"):
+            tx = U.TxChain(U.default_tx_config(dmod_mode=U.DEMOD_DIGI, iq_freq_mode=0), channels=C, frames=N, stream=s.cuda_stream)
+            if kind == "rtty":
+                tx.set_rtty_mod(True, capacity=64)
+            else:
+                tx.set_psk_mod(True, speed=2, capacity=64)
+            if not a.serial:
+                tx.set_pipelined(True)
+            tx.mod_put_text([texts[c % 4] for c in range(C)])
+            iq = torch.empty((C, N, 2), dtype=torch.int32, device="cuda")
+            a0 = torch.empty((C, N), dtype=torch.float32, device="cuda")
+            ms = time_calls(lambda: tx.process_digi(iq, a0), a.steps, a.warmup, None if a.serial else tx.join)
+            # 8 B I/Q frame out and the 4 B a0 copy; the int16 row and the f32 hand-off between kernels
+            # written and read once; state (Hilbert 200, lattice 10, modulator 13 words) once per call
+            per = 8 + 4 + 2 * 2 + 2 * 4 + 2 * 4 * (200 + 10 + 13) / N
+            lines.append({"workload": f"C4 per-GPU share: DIGI-TX {'RTTY 170/45' if kind == 'rtty' else 'BPSK125'} (modulator + IIR_TX_SOPRANO + 201-tap Hilbert, zero IF)",
+                          "precision": "exact", "channels": C, "frames_per_call": N, "pipelined": not a.serial, "ms_per_call": round(ms, 4),
+                          "msamples_per_s": round(C * N / ms / 1e3, 1), "alg_bytes_per_frame": round(per, 2),
+                          "hbm_frac": round(C * N * per / ms / 1e6 / HBM_PEAK_GBS, 4),
+                          "finite": bool(torch.isfinite(a0).all().item()) and bool((iq != 0).any().item())})
+            tx.close()
     if "c5" in want:
         C, N = 1048576 // 8, 256
         cfg = U.default_config(filter_path=4, dmod_mode=U.DEMOD_CW)

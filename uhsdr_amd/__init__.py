@@ -24,3 +24,4 @@ from .fir import FirBatch  # noqa: F401
 from .cwdec import CwDecoder  # noqa: F401
 from .rtty import RttyDecoder  # noqa: F401
 from .psk import PskDecoder  # noqa: F401
+from .digimod import RttyModulator, PskModulator  # noqa: F401

@@ -111,7 +111,7 @@ class TxConfig(C.Structure):
         ("treble_gain", C.c_int32), ("filter_disable", C.c_int32), ("power_factor", C.c_float),
         ("gain_i", C.c_float), ("gain_q", C.c_float), ("phase_balance", C.c_float),
         ("fm_deviation_5k", C.c_int32), ("fm_subaudible_tone", C.c_int32), ("fm_tone_burst_mode", C.c_int32),
-        ("reserved", C.c_int32 * 13),
+        ("digi_lsb", C.c_int32), ("reserved", C.c_int32 * 12),
     ]
 
 
@@ -221,6 +221,11 @@ SIGNATURES = {
     "uhsdr_tx_join": (C.c_int, [C.c_void_p]),
     "uhsdr_tx_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "uhsdr_tx_get_precision": (C.c_int32, [C.c_void_p]),
+    "uhsdr_tx_set_rtty_mod": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "uhsdr_tx_set_psk_mod": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "uhsdr_tx_mod_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uhsdr_tx_mod_start": (C.c_int, [C.c_void_p]),
+    "uhsdr_tx_mod_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "uhsdr_fir_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "uhsdr_fir_reset": (C.c_int, [C.c_void_p]),
@@ -282,7 +287,25 @@ SIGNATURES = {
     "uhsdr_psk_destroy": (C.c_int, [C.c_void_p]),
     "uhsdr_rx_set_psk_text": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "uhsdr_rx_psk_text_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "uhsdr_rttymod_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_rttymod_create_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "uhsdr_rttymod_start_tx": (C.c_int, [C.c_void_p]),
+    "uhsdr_pskmod_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_pskmod_create_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "uhsdr_pskmod_prepare_tx": (C.c_int, [C.c_void_p]),
 }
+# the calls uhsdr_rttymod_* and uhsdr_pskmod_* have in common
+for _m in ("rttymod", "pskmod"):
+    SIGNATURES.update({
+        f"uhsdr_{_m}_reset": (C.c_int, [C.c_void_p]),
+        f"uhsdr_{_m}_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+        f"uhsdr_{_m}_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+        f"uhsdr_{_m}_process_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+        f"uhsdr_{_m}_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+        f"uhsdr_{_m}_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+        f"uhsdr_{_m}_synchronize": (C.c_int, [C.c_void_p]),
+        f"uhsdr_{_m}_destroy": (C.c_int, [C.c_void_p]),
+    })
 
 _lib = None
 
@@ -401,7 +424,7 @@ TX_ARG_MAP = {
     "comp": "comp_level", "txfilter": "tx_filter", "txbass": "bass_gain", "txtreble": "treble_gain",
     "txpwr": "power_factor", "txgi": "gain_i", "txgq": "gain_q", "txphase": "phase_balance",
     "fm5k": "fm_deviation_5k", "subtone": "fm_subaudible_tone", "burstmode": "fm_tone_burst_mode",
-    "txsrc": "audio_source",
+    "txsrc": "audio_source", "digilsb": "digi_lsb",
 }
 FLAGS1_AM_TX_FILTER_DISABLE, FLAGS1_SSB_TX_FILTER_DISABLE = 0x08, 0x40   # hardware/uhsdr_board.h:513,516
 TUNE_OFF, TUNE_SINGLE, TUNE_TWO = range(3)      # uhsdr_tx_set_tune

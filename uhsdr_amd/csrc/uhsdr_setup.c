@@ -600,9 +600,15 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
 {
     if (!cfg || !p) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
     const int fm = cfg->dmod_mode == UHSDR_DEMOD_FM, am = cfg->dmod_mode == UHSDR_DEMOD_AM;
-    if (cfg->dmod_mode != UHSDR_DEMOD_USB && cfg->dmod_mode != UHSDR_DEMOD_LSB && !fm && !am)
+    const int digi = cfg->dmod_mode == UHSDR_DEMOD_DIGI;
+    if (cfg->dmod_mode != UHSDR_DEMOD_USB && cfg->dmod_mode != UHSDR_DEMOD_LSB && !fm && !am && !digi)
     {
-        uhsdr_set_error("transmit mode %d: SSB (USB/LSB), AM and FM voice are implemented", cfg->dmod_mode);
+        uhsdr_set_error("transmit mode %d: SSB (USB/LSB), AM and FM voice and DIGI (RTTY / BPSK) are implemented", cfg->dmod_mode);
+        return UHSDR_UNSUPPORTED;
+    }
+    if (digi && cfg->audio_source == UHSDR_TX_AUDIO_DIGIQ)
+    {
+        uhsdr_set_error("DIGI transmit with the USB I/Q source is not implemented");
         return UHSDR_UNSUPPORTED;
     }
     if ((fm || am) && cfg->iq_freq_mode == UHSDR_IQ_CONV_OFF && cfg->audio_source != UHSDR_TX_AUDIO_DIGIQ)
@@ -631,7 +637,8 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
     }
     memset(p, 0, sizeof *p);
     p->dmod_mode = cfg->dmod_mode;
-    p->lsb = cfg->dmod_mode == UHSDR_DEMOD_LSB;
+    /* DIGI: TxProcessor_SSB(..., 0, ts.digi_lsb) (tx_processor.c:819, :842) */
+    p->lsb = digi ? cfg->digi_lsb != 0 : cfg->dmod_mode == UHSDR_DEMOD_LSB;
     p->audio_source = cfg->audio_source;
 
     /* TxProcessor_AudioBufferFill gain (tx_processor.c:354-381) */
@@ -656,7 +663,7 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
 
     /* TxProcessor_FilterAudio: lattice band-pass unless disabled (FM always filters,
        tx_processor.c:1012), biquads for codec sources; FM uses IIR_TX_2k7_FM (:104-107) */
-    p->run_lattice = fm || !cfg->filter_disable;           /* FLAGS1_SSB / _AM_TX_FILTER_DISABLE (:991, :1003) */
+    p->run_lattice = fm || digi || !cfg->filter_disable;          /* FLAGS1_SSB / _AM_TX_FILTER_DISABLE (:991, :1003) */
     p->run_biquad = cfg->audio_source != UHSDR_TX_AUDIO_DIG;   /* do_bass_treble (:445) */
     const int sel = fm ? 3 : cfg->tx_filter == 2 ? 1 : cfg->tx_filter == 3 ? 2 : 0;   /* TENOR, BASS, default SOPRANO */
     const uhsdr_lattice_desc* l = &uhsdr_tx_lattices[sel];
@@ -697,6 +704,7 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
     case UHSDR_IQ_CONV_M12KHZ: p->freq_shift_hz = -12000; break;
     default: p->freq_shift_hz = 0; break;
     }
+    if (digi) p->freq_shift_hz = 0;     /* the modulators' signal stays around the centre frequency */
     if (p->freq_shift_hz != 0)
     {
         const int32_t conv = p->freq_shift_hz < 0 ? -p->freq_shift_hz : p->freq_shift_hz;

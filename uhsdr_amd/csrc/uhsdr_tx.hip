@@ -420,6 +420,54 @@ __global__ void __launch_bounds__(128) tx_voice2(TxVoiceArgs a)
     }
 }
 
+// The voice stage of DIGI transmit (TxProcessor_Rtty / TxProcessor_Psk, tx_processor.c:811-845):
+// the modulator's int16 row instead of the codec frames, the TX band-pass lattice
+// (TxProcessor_FilterAudio(true, false)) and nothing else: no input gain, no biquads, no ALC.
+// A kernel of its own, so tx_voice and tx_voice2 stay as they are.  One lane per channel, the
+// packed lattice paired by the sample's parity exactly as tx_voice does it.
+template <int S>
+__global__ void __launch_bounds__(64) tx_voice_digi(const uhsdr_tx_plan* __restrict__ P, const int16_t* __restrict__ mod,
+                                                    float* __restrict__ txa, float* __restrict__ a0, float* __restrict__ lat, int C, int N)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    const bool live = c < C;
+    const int cl = live ? c : C - 1;
+    float lk[S], lv[S + 1], g[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) lk[i] = P->lat_k[i];
+#pragma unroll
+    for (int i = 0; i <= S; ++i) lv[i] = P->lat_v[i];
+#pragma unroll
+    for (int i = 0; i < S; ++i) g[i] = lat[i * C + cl];
+    for (int k = 0; k < N / BLK; ++k)
+    {
+        float x[BLK];
+        const int16_t* src = mod + (size_t)cl * N + k * BLK;      // [C][N], N a multiple of 32
+#pragma unroll
+        for (int m = 0; m < BLK; ++m) x[m] = (float)src[m];
+#pragma unroll
+        for (int m = 0; m < BLK; ++m)
+            x[m] = (m & 1) ? lattice_step_pk<S, 1>(x[m], g, lk, lv) : lattice_step_pk<S, 0>(x[m], g, lk, lv);
+        if (live)
+        {
+            float* d0 = a0 ? a0 + (size_t)c * N + k * BLK : nullptr;
+            float* dst = txa + (size_t)c * N + k * BLK;
+#pragma unroll
+            for (int m = 0; m < BLK; m += 4)
+            {
+                const float4 v = make_float4(x[m], x[m + 1], x[m + 2], x[m + 3]);
+                *(float4*)(dst + m) = v;
+                if (d0) *(float4*)(d0 + m) = v;
+            }
+        }
+    }
+    if (live)
+    {
+#pragma unroll
+        for (int i = 0; i < S; ++i) lat[i * C + c] = g[i];
+    }
+}
+
 struct TxIqArgs
 {
     const uhsdr_tx_plan* plan;
@@ -598,6 +646,11 @@ struct uhsdr_tx_s
     hipEvent_t ev_voice, ev_join, ev_iq[2];
     float* txa2;                     // the second hand-off buffer [C][N]
     int precision;                   // uhsdr_tx_set_precision
+    // DIGI transmit: the modulator the handle owns (one of the two) and its int16 row [C][N]
+    uhsdr_rttymod_handle rmod;
+    uhsdr_pskmod_handle pmod;
+    int16_t* mod_row;
+    float ssb_i_gain, ssb_q_gain;    // the plan's final gains with SSB_GAIN_COMP (RTTY); BPSK runs with iq_gain_comp 1.0
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
@@ -652,12 +705,20 @@ extern "C" uhsdr_status uhsdr_tx_reset(uhsdr_tx_handle h)
     h->calls_done = 0;
     h->iq_launches = 0;
     h->calls_issued = 0;
+    if (h->rmod) return uhsdr_rttymod_reset(h->rmod);
+    if (h->pmod) return uhsdr_pskmod_reset(h->pmod);
     return UHSDR_OK;
 }
 
 extern "C" uhsdr_status uhsdr_tx_set_tune(uhsdr_tx_handle h, int32_t tune)
 {
     if (!h || tune < UHSDR_TUNE_OFF || tune > UHSDR_TUNE_TWO) { uhsdr_set_error("bad argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (h->plan.dmod_mode == UHSDR_DEMOD_DIGI)
+    {
+        // the firmware's dvmode branch (tx_processor.c:962-984) never looks at ts.tune
+        uhsdr_set_error("TUNE on a DIGI transmit handle");
+        return UHSDR_ARGUMENT_ERROR;
+    }
     // AudioManagement_SetSidetoneForDemodMode -> softdds_configRunIQ(freq, rate, smooth = 0): both
     // accumulators restart at 0, on entering and on leaving TUNE (audio_management.c:377-404)
     h->tune = tune;
@@ -736,13 +797,21 @@ extern "C" uhsdr_status uhsdr_tx_create(const uhsdr_tx_config* cfg, int32_t C, i
         uhsdr_set_error("plan upload failed");
         return UHSDR_DEVICE_ERROR;
     }
+    h->ssb_i_gain = h->plan.final_i_gain;
+    h->ssb_q_gain = h->plan.final_q_gain;
     *out = h;
     return uhsdr_tx_reset(h);
 }
 
 extern "C" uhsdr_status uhsdr_tx_process(uhsdr_tx_handle h, const int32_t* audio, int32_t* iq, float* a0)
 {
-    if (!h || !audio || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    const bool digi = h && h->plan.dmod_mode == UHSDR_DEMOD_DIGI;
+    if (!h || (!audio && !digi) || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (digi && !h->rmod && !h->pmod)
+    {
+        uhsdr_set_error("DIGI transmit without a modulator: uhsdr_tx_set_rtty_mod or uhsdr_tx_set_psk_mod first");
+        return UHSDR_ARGUMENT_ERROR;
+    }
     if (h->plan.digiq && !h->tune)
     {
         // USB I/Q source: no voice chain, no modulator state advances, a0 (adb.a_buffer[0]) untouched.
@@ -796,7 +865,16 @@ extern "C" uhsdr_status uhsdr_tx_process(uhsdr_tx_handle h, const int32_t* audio
         h->calls_done += h->N / BLK;
         return UHSDR_OK;
     }
-    hipLaunchKernelGGL(tx_voice2<10>, dim3((h->C + 63) / 64), dim3(128), 0, h->stream, va);
+    if (digi)
+    {
+        // N samples of every channel's modulator into the handle's row, then the lattice over it
+        const uhsdr_status ms = h->rmod ? uhsdr_rttymod_process(h->rmod, h->mod_row, h->N, h->N)
+                                        : uhsdr_pskmod_process(h->pmod, h->mod_row, h->N, h->N);
+        if (ms != UHSDR_OK) return ms;
+        hipLaunchKernelGGL(tx_voice_digi<10>, dim3((h->C + 63) / 64), dim3(64), 0, h->stream, h->d_plan, h->mod_row, txa, a0,
+                           h->lat, h->C, h->N);
+    }
+    else hipLaunchKernelGGL(tx_voice2<10>, dim3((h->C + 63) / 64), dim3(128), 0, h->stream, va);
     HIPCHK(hipGetLastError());
     const hipStream_t ist = h->pipelined ? h->side : h->stream;
     if (h->pipelined)
@@ -824,6 +902,99 @@ extern "C" uhsdr_status uhsdr_tx_process(uhsdr_tx_handle h, const int32_t* audio
     h->calls_issued += 1;
     h->calls_done += h->N / BLK;
     return UHSDR_OK;
+}
+
+// ---- DIGI transmit: the modulator inside the chain ----
+
+static void tx_drop_mod(uhsdr_tx_s* h)
+{
+    if (h->rmod) (void)uhsdr_rttymod_destroy(h->rmod);
+    if (h->pmod) (void)uhsdr_pskmod_destroy(h->pmod);
+    if (h->mod_row) (void)hipFree(h->mod_row);
+    h->rmod = nullptr; h->pmod = nullptr; h->mod_row = nullptr;
+}
+
+static uhsdr_status tx_check_digi(uhsdr_tx_handle h)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (h->plan.dmod_mode != UHSDR_DEMOD_DIGI) { uhsdr_set_error("not a DIGI transmit handle (dmod_mode %d)", h->plan.dmod_mode); return UHSDR_ARGUMENT_ERROR; }
+    return UHSDR_OK;
+}
+
+// the final stage's gains of the plan: iq_gain_comp is SSB_GAIN_COMP for RTTY and 1.0 for BPSK
+// (tx_processor.c:976, :981); the plan holds both products (final_*_gain, digiq_*_gain)
+static uhsdr_status tx_set_final_gain(uhsdr_tx_s* h, bool unity)
+{
+    if (tx_join(h) != UHSDR_OK) return UHSDR_DEVICE_ERROR;
+    HIPCHK(hipStreamSynchronize(h->stream));        // no launch still reads the plan
+    h->plan.final_i_gain = unity ? h->plan.digiq_i_gain : h->ssb_i_gain;
+    h->plan.final_q_gain = unity ? h->plan.digiq_q_gain : h->ssb_q_gain;
+    HIPCHK(hipMemcpy(h->d_plan, &h->plan, sizeof(uhsdr_tx_plan), hipMemcpyHostToDevice));
+    return UHSDR_OK;
+}
+
+static uhsdr_status tx_mod_row(uhsdr_tx_s* h)
+{
+    if (!h->mod_row) HIPCHK(hipMalloc((void**)&h->mod_row, sizeof(int16_t) * (size_t)h->C * h->N));
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_set_rtty_mod(uhsdr_tx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
+                                              int32_t text_capacity)
+{
+    uhsdr_status st = tx_check_digi(h);
+    if (st != UHSDR_OK) return st;
+    if (!enable) { if (h->rmod) { if ((st = tx_set_final_gain(h, false)) != UHSDR_OK) return st; tx_drop_mod(h); } return UHSDR_OK; }
+    if (h->pmod) { uhsdr_set_error("the BPSK modulator is on: one modulator at a time"); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_rttymod_handle m = nullptr;
+    if ((st = uhsdr_rttymod_create(h->C, shift_idx, speed_idx, stopbits_idx, text_capacity, h->stream, &m)) != UHSDR_OK) return st;
+    if ((st = tx_set_final_gain(h, false)) != UHSDR_OK || (st = tx_mod_row(h)) != UHSDR_OK) { (void)uhsdr_rttymod_destroy(m); return st; }
+    if (h->rmod) (void)uhsdr_rttymod_destroy(h->rmod);
+    h->rmod = m;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_set_psk_mod(uhsdr_tx_handle h, int32_t enable, int32_t speed_idx, int32_t text_capacity)
+{
+    uhsdr_status st = tx_check_digi(h);
+    if (st != UHSDR_OK) return st;
+    if (!enable) { if (h->pmod) { if ((st = tx_set_final_gain(h, false)) != UHSDR_OK) return st; tx_drop_mod(h); } return UHSDR_OK; }
+    if (h->rmod) { uhsdr_set_error("the RTTY modulator is on: one modulator at a time"); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_pskmod_handle m = nullptr;
+    if ((st = uhsdr_pskmod_create(h->C, speed_idx, text_capacity, h->stream, &m)) != UHSDR_OK) return st;
+    if ((st = tx_set_final_gain(h, true)) != UHSDR_OK || (st = tx_mod_row(h)) != UHSDR_OK) { (void)uhsdr_pskmod_destroy(m); return st; }
+    if (h->pmod) (void)uhsdr_pskmod_destroy(h->pmod);
+    h->pmod = m;
+    return UHSDR_OK;
+}
+
+static uhsdr_status tx_check_mod(uhsdr_tx_handle h)
+{
+    const uhsdr_status st = tx_check_digi(h);
+    if (st != UHSDR_OK) return st;
+    if (!h->rmod && !h->pmod) { uhsdr_set_error("no modulator enabled"); return UHSDR_ARGUMENT_ERROR; }
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_mod_put_text(uhsdr_tx_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted)
+{
+    const uhsdr_status st = tx_check_mod(h);
+    if (st != UHSDR_OK) return st;
+    return h->rmod ? uhsdr_rttymod_put_text(h->rmod, text, len, stride, accepted) : uhsdr_pskmod_put_text(h->pmod, text, len, stride, accepted);
+}
+
+extern "C" uhsdr_status uhsdr_tx_mod_start(uhsdr_tx_handle h)
+{
+    const uhsdr_status st = tx_check_mod(h);
+    if (st != UHSDR_OK) return st;
+    return h->rmod ? uhsdr_rttymod_start_tx(h->rmod) : uhsdr_pskmod_prepare_tx(h->pmod);
+}
+
+extern "C" uhsdr_status uhsdr_tx_mod_outputs(uhsdr_tx_handle h, uint32_t** consumed, uint32_t** txoff_at, uint8_t** state)
+{
+    const uhsdr_status st = tx_check_mod(h);
+    if (st != UHSDR_OK) return st;
+    return h->rmod ? uhsdr_rttymod_outputs(h->rmod, consumed, txoff_at, state) : uhsdr_pskmod_outputs(h->pmod, consumed, txoff_at, state);
 }
 
 extern "C" uhsdr_status uhsdr_tx_set_precision(uhsdr_tx_handle h, int32_t precision)
@@ -895,6 +1066,7 @@ extern "C" uhsdr_status uhsdr_tx_destroy(uhsdr_tx_handle h)
         for (int i = 0; i < 2; ++i) (void)hipEventDestroy(h->ev_iq[i]);
     }
     if (h->txa2) (void)hipFree(h->txa2);
+    tx_drop_mod(h);
     (void)hipFree(h->arena);
     (void)hipFree(h->d_plan);
     (void)hipFree(h->d_taps2);

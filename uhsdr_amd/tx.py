@@ -69,6 +69,58 @@ class TxChain:
         """FM tone burst (whistle-up) on / off for the following calls."""
         _abi.check(self.lib.uhsdr_tx_set_tone_burst(self.handle, int(bool(active))), "uhsdr_tx_set_tone_burst")
 
+    # ---- DIGI transmit (dmod_mode DEMOD_DIGI): the modulator inside the chain ----
+
+    def set_rtty_mod(self, enable: bool, shift: int = 1, speed: int = 0, stopbits: int = 1, capacity: int = 128) -> None:
+        """the handle's RTTY modulator on / off (uhsdr_tx_set_rtty_mod; arguments as RttyModulator)"""
+        _abi.check(self.lib.uhsdr_tx_set_rtty_mod(self.handle, int(bool(enable)), int(shift), int(speed), int(stopbits), int(capacity)),
+                   "uhsdr_tx_set_rtty_mod")
+
+    def set_psk_mod(self, enable: bool, speed: int = 0, capacity: int = 128) -> None:
+        """the handle's BPSK modulator on / off (uhsdr_tx_set_psk_mod; arguments as PskModulator)"""
+        _abi.check(self.lib.uhsdr_tx_set_psk_mod(self.handle, int(bool(enable)), int(speed), int(capacity)), "uhsdr_tx_set_psk_mod")
+
+    def mod_put_text(self, text):
+        """text: one bytes object per channel (or one for all); returns the accepted counts int32 [C]"""
+        import numpy as np
+        if isinstance(text, (bytes, bytearray)):
+            text = [bytes(text)] * self.channels
+        if len(text) != self.channels:
+            raise ValueError("one text per channel")
+        length = np.array([len(t) for t in text], np.int32)
+        stride = max(1, int(length.max()))
+        rows = np.zeros((self.channels, stride), np.uint8)
+        for c, t in enumerate(text):
+            rows[c, :len(t)] = np.frombuffer(bytes(t), np.uint8)
+        accepted = np.zeros(self.channels, np.int32)
+        _abi.check(self.lib.uhsdr_tx_mod_put_text(self.handle, rows.ctypes.data_as(C.c_void_p), length.ctypes.data_as(C.c_void_p),
+                                                  stride, accepted.ctypes.data_as(C.c_void_p)), "uhsdr_tx_mod_put_text")
+        return accepted
+
+    def mod_start(self) -> None:
+        """Rtty_Modulator_StartTX / Psk_Modulator_PrepareTx on every channel"""
+        _abi.check(self.lib.uhsdr_tx_mod_start(self.handle), "uhsdr_tx_mod_start")
+
+    def mod_outputs(self):
+        """(consumed uint32 [C], txoff_at uint32 [C], state uint8 [C]) as host arrays; the work enqueued must be complete"""
+        import numpy as np
+        p = [C.c_void_p() for _ in range(3)]
+        _abi.check(self.lib.uhsdr_tx_mod_outputs(self.handle, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])), "uhsdr_tx_mod_outputs")
+        out = []
+        for ptr, dtype in zip(p, (np.uint32, np.uint32, np.uint8)):
+            arr = np.empty(self.channels, dtype)
+            _abi.check(self.lib.uhsdr_copy_to_host(arr.ctypes.data_as(C.c_void_p), ptr, arr.nbytes), "uhsdr_copy_to_host")
+            out.append(arr)
+        return tuple(out)
+
+    def process_digi(self, iq, a0=None) -> None:
+        """uhsdr_tx_process with a modulator on: no audio input"""
+        want = (self.channels, self.frames, 2)
+        if tuple(iq.shape) != want or (a0 is not None and tuple(a0.shape) != want[:2]):
+            raise ValueError(f"iq must be {want}, a0 {want[:2]}")
+        _abi.check(self.lib.uhsdr_tx_process(self.handle, None, C.c_void_p(iq.data_ptr()),
+                                             C.c_void_p(a0.data_ptr() if a0 is not None else 0)), "uhsdr_tx_process")
+
     def close(self) -> None:
         if self.handle:
             self.lib.uhsdr_tx_destroy(self.handle)
