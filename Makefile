@@ -2,7 +2,8 @@
 #
 #   make            -> uhsdr_amd/lib/libuhsdr_amd.so   (product: C-ABI, HIP kernels + host setup)
 #                      oracle/build/libuhsdr_oracle.so (test infrastructure: CPU restatement)
-#   make ref        -> oracle/_ref/uhsdr_ref           (reference firmware chain, needs /root/reference)
+#                      tests/build/libuhsdr_libm_probe{,_host}.so (test-only libm probes)
+#   make ref        -> oracle/_ref/uhsdr_ref          (reference firmware chain, needs /root/reference)
 #
 # Host C is compiled without FP contraction and without -march, like the reference build,
 # so every binary32 rounding of the setup math and of the oracle matches the reference.
@@ -26,10 +27,21 @@ HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsd
 
 EXAMPLE := examples/build/rx_batch
 
-all: $(LIB) $(CMSISLIB) $(ORACLE) $(EXAMPLE)
+# test-only probes of uhsdr_libm.h and the IEEE primitives (tests/test_gpu_libm.py): the device
+# build under exactly the product's HIPFLAGS, the host build under exactly HOSTCFLAGS
+PROBE      := tests/build/libuhsdr_libm_probe.so
+PROBE_HOST := tests/build/libuhsdr_libm_probe_host.so
 
-$(OBJDIR) uhsdr_amd/lib oracle/build:
+all: $(LIB) $(CMSISLIB) $(ORACLE) $(EXAMPLE) $(PROBE) $(PROBE_HOST)
+
+$(OBJDIR) uhsdr_amd/lib oracle/build tests/build:
 	mkdir -p $@
+
+$(PROBE): tests/device/libm_probe.hip uhsdr_amd/csrc/uhsdr_libm.h | tests/build
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+
+$(PROBE_HOST): tests/device/libm_probe_host.c uhsdr_amd/csrc/uhsdr_libm.h | tests/build
+	$(CC) $(HOSTCFLAGS) -shared -o $@ $< -lm
 
 $(OBJDIR)/%.o: uhsdr_amd/csrc/%.c $(HDRS) | $(OBJDIR)
 	$(CC) $(HOSTCFLAGS) -c $< -o $@
@@ -62,7 +74,7 @@ ref:
 	$(MAKE) -C oracle/ref
 
 clean:
-	rm -rf $(OBJDIR) uhsdr_amd/lib oracle/build examples/build
+	rm -rf $(OBJDIR) uhsdr_amd/lib oracle/build examples/build tests/build
 
 .PHONY: all ref clean
 

@@ -1,6 +1,7 @@
 /* Pins uhsdr_amd/csrc/uhsdr_libm.h against the host's libm (glibc).
  *   libm_check sincos <stride>   every stride-th float in [0, 2*pi] and (-2*pi, 0)
  *   libm_check atan2 <count>     random + structured operand pairs
+ *   libm_check pairs <count>     the operand pairs of "atan2 <count>" as raw binary32 (y, x) on stdout, no check
  *   libm_check asin <stride>     every stride-th float in [-1, 1] (and NaN operands past it)
  *   libm_check atan2x1 <stride>  every stride-th binary32 y (all signs) against atan2f(y, 1.0f)
  *   libm_check atanpos <stride>  ul_atanf_pos (atan2f's reduction) on every stride-th float in [0, inf]
@@ -88,6 +89,7 @@ int main(int argc, char** argv)
     else
     {
         const long count = atol(argv[2]);
+        const int dump = !strcmp(argv[1], "pairs");
         const float special[] = { 0.0f, -0.0f, 1.0f, -1.0f, INFINITY, -INFINITY, NAN, 1e-30f, -1e-30f, 3e38f, -3e38f,
                                   1e-45f, -1e-45f, 0.5f, 2.0f, 1.5f, 0.4375f, 1.1875f, 2.4375f, 0.6875f };
         const int ns = sizeof special / sizeof special[0];
@@ -102,6 +104,7 @@ int main(int argc, char** argv)
                 const int e = (int)(next32() % 40) - 20;
                 y = ldexpf(a, e); x = ldexpf(b, e + (int)(next32() % 9) - 4);
             }
+            if (dump) { fwrite(&y, 4, 1, stdout); fwrite(&x, 4, 1, stdout); continue; }
             const float r0 = atan2f(y, x), r1 = ul_atan2f(y, x);
             ++n;
             if (ul_asuint(r0) != ul_asuint(r1) && !(isnan(r0) && isnan(r1)))
@@ -109,7 +112,7 @@ int main(int argc, char** argv)
                 if (bad++ < 10) printf("atan2f(%a, %a): glibc %a, ours %a\n", y, x, r0, r1);
             }
         }
-        printf("atan2f: %ld of %ld operand pairs differ\n", bad, n);
+        if (!dump) printf("atan2f: %ld of %ld operand pairs differ\n", bad, n);
     }
     return bad != 0;
 }

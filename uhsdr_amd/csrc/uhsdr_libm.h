@@ -16,7 +16,9 @@
  *            arithmetic, no IFUNC variant.
  *
  * Pinned against the host's libm by tests/test_libm.py (every float in [0, 2*pi] for
- * sincosf -- the PLL phase range -- plus random and special operands for atan2f).
+ * sincosf -- the PLL phase range -- plus random and special operands for atan2f), and the
+ * device build against this host build and against recorded glibc 2.35 results, on the MI355X,
+ * by tests/test_gpu_libm.py (tests/device/libm_probe.hip, built with the product's flags).
  * Compiled by hipcc for the device and by gcc (-ffp-contract=off) for the host check;
  * the fused operations are explicit fma() calls, so no compiler contraction is involved.
  */
