@@ -433,7 +433,7 @@ enum { UHSDR_TX_AUDIO_MIC = 0, UHSDR_TX_AUDIO_LINEIN_L = 1, UHSDR_TX_AUDIO_LINEI
 
 typedef struct uhsdr_tx_config
 {
-    int32_t dmod_mode;            /* ts.dmod_mode: UHSDR_DEMOD_USB, _LSB, _AM, _FM or _DIGI (uhsdr_tx_set_rtty_mod) */
+    int32_t dmod_mode;            /* ts.dmod_mode: UHSDR_DEMOD_USB, _LSB, _AM, _FM, _DIGI (uhsdr_tx_set_rtty_mod) or _CW (uhsdr_tx_set_cw_keyer) */
     int32_t iq_freq_mode;         /* ts.iq_freq_mode */
     int32_t audio_source;         /* ts.tx_audio_source: MIC, LINEIN_L, LINEIN_R, DIG, DIGIQ */
     int32_t mic_gain_mult;        /* ts.tx_mic_gain_mult (codec.c:313-321) */
@@ -453,7 +453,10 @@ typedef struct uhsdr_tx_config
     int32_t fm_tone_burst_mode;   /* ts.fm_tone_burst_mode: 0 off, 1 1750 Hz, 2 2135 Hz (fm_tone_burst_freq,
                                      audio_management.c:328), sent while uhsdr_tx_set_tone_burst is on */
     int32_t digi_lsb;             /* ts.digi_lsb: UHSDR_DEMOD_DIGI transmits on the lower sideband */
-    int32_t reserved[12];
+    int32_t cw_lsb;               /* ts.cw_lsb: UHSDR_DEMOD_CW exchanges I and Q (tx_processor.c:860-863) */
+    /* the keyer of UHSDR_DEMOD_CW, as uhsdr_cwgen_config (defaults IAM_B, 20 wpm, weight 100, rx_delay 8, 750 Hz) */
+    int32_t cw_keyer_mode, cw_keyer_speed, cw_keyer_weight, cw_paddle_reverse, cw_rx_delay, cw_sidetone_freq;
+    int32_t reserved[5];
 } uhsdr_tx_config;
 
 typedef struct uhsdr_tx_plan
@@ -493,8 +496,10 @@ typedef struct uhsdr_tx_plan
     float   tone_burst_scale;     /* FM_TONE_BURST_AMPLITUDE_SCALING * fm_mod_mult */
     int32_t am;                   /* TxProcessor_AM: both sidebands + carrier after the Hilbert pair */
     int32_t digiq;                /* TX_AUDIO_DIGIQ: the input frames are I/Q for the final stage */
-    float   digiq_i_gain, digiq_q_gain;   /* final gains with iq_gain_comp 1.0 (tx_processor.c:924) */
-    int32_t reserved[24];
+    float   digiq_i_gain, digiq_q_gain;   /* final gains with iq_gain_comp 1.0 (tx_processor.c:924); CW runs with these */
+    int32_t cw;                   /* UHSDR_DEMOD_CW: TxProcessor_CW, lsb = cw_lsb */
+    int32_t cw_keyer_mode, cw_keyer_speed, cw_keyer_weight, cw_paddle_reverse, cw_rx_delay, cw_sidetone_freq;
+    int32_t reserved[17];
 } uhsdr_tx_plan;
 
 typedef struct uhsdr_tx_s* uhsdr_tx_handle;
@@ -562,6 +567,31 @@ uhsdr_status uhsdr_tx_set_tone_burst(uhsdr_tx_handle h, int32_t active);
    mod_put_text, mod_start (StartTX / PrepareTx) and mod_outputs are the modulator's put_text,
    start_tx / prepare_tx and outputs.  Not built: the keyer as text entry
    (TxProcessor_CwInputForDigitalModes with a keyer mode other than STRAIGHT) and the OVI40 sidetone. */
+typedef struct uhsdr_cwgen_s* uhsdr_cwgen_handle;
+/* CW transmit (dmod_mode UHSDR_DEMOD_CW; TxProcessor_CW, tx_processor.c:856-888, :985-988): the handle
+   owns one CW generator (uhsdr_cwgen_* below) with the config's keyer settings.  uhsdr_tx_process
+   ignores `audio` (it may be null) and runs one kernel, tx_cw: the keyer, tone and envelope of every
+   32-frame block, the exchange of I and Q unless cw_lsb (the generator's sine goes to Q in USB), a0 =
+   the generator's I while the signal is active and 0 otherwise, and the final stage with iq_gain_comp
+   1.0 (gain_i / gain_q are the IQ_TRANS_OFF gains: CW transmits at zero IF whatever iq_freq_mode says),
+   the phase balance and the int32 DAC frames.  No lattice, ALC, Hilbert pair or frequency shift.
+     set_cw_keyer(text_capacity, echo_capacity)  creates the generator (again: a fresh one)
+     cw_keys(keys)     device uint8 [C][N/32], read by the following uhsdr_tx_process calls
+     cw_put_text, cw_set_speed, cw_outputs   as uhsdr_cwgen_put_text / _set_speed / _outputs
+   uhsdr_tx_set_tune (any mode but OFF): the continuous 750 Hz tone, every block active, the keyer
+   stands still and the key bytes are not looked at; the tone's phase restarts at 0 on entering and
+   on leaving.  uhsdr_tx_reset resets the keyer; uhsdr_tx_prepare_run leaves it alone.
+   uhsdr_tx_set_pipelined and uhsdr_tx_set_precision are accepted and change nothing (one kernel, no
+   FIR).  UHSDR_ARGUMENT_ERROR: these calls on a handle of another mode, the modulator calls on a CW
+   handle, uhsdr_tx_process before set_cw_keyer or, outside TUNE, before cw_keys, and the USB I/Q
+   source with CW at create.
+   Not built: the keyer as text entry for RTTY / BPSK, CAT keying, the OVI40 sidetone, uhsdr_i2s_*
+   with a CW transmitter, PTT sequencing (the TX-on / TX-off flags are outputs). */
+uhsdr_status uhsdr_tx_set_cw_keyer(uhsdr_tx_handle h, int32_t text_capacity, int32_t echo_capacity);
+uhsdr_status uhsdr_tx_cw_keys(uhsdr_tx_handle h, const uint8_t* keys);
+uhsdr_status uhsdr_tx_cw_put_text(uhsdr_tx_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted);
+uhsdr_status uhsdr_tx_cw_set_speed(uhsdr_tx_handle h, int32_t speed, int32_t weight);
+uhsdr_status uhsdr_tx_cw_outputs(uhsdr_tx_handle h, uint8_t** flags, uint32_t** consumed, uint8_t** echo, uint32_t** echo_total, uint8_t** state);
 uhsdr_status uhsdr_tx_set_rtty_mod(uhsdr_tx_handle h, int32_t enable, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
                                    int32_t text_capacity);
 uhsdr_status uhsdr_tx_set_psk_mod(uhsdr_tx_handle h, int32_t enable, int32_t speed_idx, int32_t text_capacity);
@@ -848,7 +878,7 @@ uhsdr_status uhsdr_psk_destroy(uhsdr_psk_handle h);
  * Inside the transmit chain (TxProcessor_Rtty / TxProcessor_Psk): uhsdr_tx_set_rtty_mod /
  * uhsdr_tx_set_psk_mod above.
  * Not built: a QPSK modulator (the firmware has none), the firmware's consumer tag on the ring, the
- * CW generator / keyer as a text source, FreeDV. */
+ * CW generator / keyer as a text source (the keyer itself is uhsdr_cwgen_* below), FreeDV. */
 typedef struct uhsdr_rttymod_s* uhsdr_rttymod_handle;
 typedef struct uhsdr_pskmod_s* uhsdr_pskmod_handle;
 
@@ -878,6 +908,77 @@ uhsdr_status uhsdr_pskmod_outputs(uhsdr_pskmod_handle h, uint32_t** consumed, ui
 uhsdr_status uhsdr_pskmod_set_stream(uhsdr_pskmod_handle h, void* stream);
 uhsdr_status uhsdr_pskmod_synchronize(uhsdr_pskmod_handle h);
 uhsdr_status uhsdr_pskmod_destroy(uhsdr_pskmod_handle h);
+
+/* ---- CW generator: key lines and text to 48 ksps I/Q, one keyer per channel ----
+ * What the firmware's CwGen_Process (drivers/audio/cw/cw_gen.c) produces per 32-sample block: the
+ * straight key or the iambic A / B / Ultimatic keyer, the softdds tone while an element is keyed,
+ * the key-click envelope on both edges, text from the queue keyed as Morse, and the characters the
+ * keyer recognises printed to an echo ring.  Exact to the reference: the same binary32 I and Q at
+ * every sample, the same state after every block.  Integer arithmetic except the envelope product.
+ * The settings are handle-wide, as the firmware's are one set per transceiver:
+ *   keyer_mode 0 IAM_B, 1 IAM_A, 2 STRAIGHT, 3 ULTIMATE; keyer_speed 5 .. 48 wpm; keyer_weight
+ *   50 .. 150; paddle_reverse; rx_delay 0 .. 50 (the break time is rx_delay * 50 + 1 blocks);
+ *   sidetone_freq 400 .. 1000 Hz
+ *   text_capacity >= 8: a channel's text queue, as the modulators' (one slot stays free)
+ *   echo_capacity >= 8: a channel's echo ring
+ * The firmware's surroundings are fixed: the transmitter is in TX in DEMOD_CW throughout, no text
+ * entry, no CAT keying, the text ring's consumer is CW.  create and reset leave every channel as
+ * CwGen_Init leaves a fresh keyer there (idle, all timers 0), the tone's phase at 0, the queue and the
+ * echo empty.  set_speed is CwGen_SetSpeed with a new speed and weight; it takes effect with the next
+ * process call, also in the middle of a character.  put_text as uhsdr_rttymod_put_text.
+ * process: keys = uint8 [C][n/32], one byte per block, bit 0 the DIT line and bit 1 the DAH/PTT line,
+ * constant over the block; i, q = f32 [C][stride]; n a multiple of 32, n <= stride; device memory
+ * (host memory for process_host), stream-ordered.  In the block where a line closes (0 -> 1 against
+ * the block before, across calls; after reset both are open) the effects of the firmware's key
+ * interrupt run first: the text queue is emptied, the character being sent is dropped, and the
+ * Ultimatic keyer notes which paddle came first.  i and q are CwGen_Process' buffers (I the sine, Q
+ * the cosine); in a block where it returns false they are written as zeros, which is what the
+ * transmit chain sends then.
+ * Outputs (device memory, or host memory for a host handle), valid once the work enqueued is complete:
+ *   flags      uint8 [C][n/32] of the last call: bit 0 CwGen_Process returned true, bit 1
+ *              RadioManagement_Request_TxOn and bit 2 RadioManagement_Request_TxOff was called in the
+ *              block.  The buffer grows with the largest call: ask again after a larger one
+ *   consumed   uint32 [C], characters taken from the queue since reset, those a key closure
+ *              discarded included
+ *   echo       uint8 [C][echo_capacity], echo_total uint32 [C]: the bytes the firmware hands to
+ *              UiDriver_TextMsgPutChar (a character, the four bytes "<XX>" of a prosign, '*' for an
+ *              unknown code, the word space), byte k at k % echo_capacity
+ *   state      uint8 [C], ps.cw_state (0 IDLE, 1 DIT_CHECK, 3 DAH_CHECK, 4 KEY_DOWN, 5 KEY_UP, 6 PAUSE,
+ *              7 WAIT); in STRAIGHT mode ps.key_timer (3 rising, 2 on, 1 falling, 0 off)
+ * peek: the keyer's words, uint32 [rows][C] (port_state, cw_state, key_timer, break_timer,
+ * space_timer, sm_tbl_ptr, ultim, cw_char, sending_char, the DDS accumulator, the key lines of the
+ * block before), for tests and diagnosis only: the rows and their order are not part of the
+ * interface and may change with any version; ask for `rows` and do not store the layout.
+ * Reference oddities kept: a character without a code is taken from the queue and dropped; cw_char
+ * wraps at 32 bits and anything above 50000 prints '*'; the straight key ignores paddle_reverse; the
+ * tone's phase is never reset by the keyer.
+ * Inside the transmit chain (TxProcessor_CW): uhsdr_tx_set_cw_keyer above.
+ * Not built: the keyer as text entry for RTTY / BPSK, CAT keying, the OVI40 sidetone, the
+ * RX-mode call of CwGen_Process, any PTT sequencing (the TX-on / TX-off requests are outputs). */
+typedef struct
+{
+    int32_t keyer_mode, keyer_speed, keyer_weight, paddle_reverse, rx_delay, sidetone_freq;
+} uhsdr_cwgen_config;
+#define UHSDR_CW_KEYER_IAM_B    0
+#define UHSDR_CW_KEYER_IAM_A    1
+#define UHSDR_CW_KEYER_STRAIGHT 2
+#define UHSDR_CW_KEYER_ULTIMATE 3
+
+uhsdr_status uhsdr_cwgen_create(int32_t num_channels, const uhsdr_cwgen_config* cfg, int32_t text_capacity, int32_t echo_capacity,
+                                void* stream, uhsdr_cwgen_handle* out);
+/* the same generator with its state in host memory, for uhsdr_cwgen_process_host (no device call) */
+uhsdr_status uhsdr_cwgen_create_host(int32_t num_channels, const uhsdr_cwgen_config* cfg, int32_t text_capacity, int32_t echo_capacity,
+                                     uhsdr_cwgen_handle* out);
+uhsdr_status uhsdr_cwgen_reset(uhsdr_cwgen_handle h);
+uhsdr_status uhsdr_cwgen_set_speed(uhsdr_cwgen_handle h, int32_t speed, int32_t weight);
+uhsdr_status uhsdr_cwgen_put_text(uhsdr_cwgen_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted);
+uhsdr_status uhsdr_cwgen_process(uhsdr_cwgen_handle h, const uint8_t* keys, float* i, float* q, int32_t n, int32_t stride);
+uhsdr_status uhsdr_cwgen_process_host(uhsdr_cwgen_handle h, const uint8_t* keys, float* i, float* q, int32_t n, int32_t stride);
+uhsdr_status uhsdr_cwgen_outputs(uhsdr_cwgen_handle h, uint8_t** flags, uint32_t** consumed, uint8_t** echo, uint32_t** echo_total, uint8_t** state);
+uhsdr_status uhsdr_cwgen_peek(uhsdr_cwgen_handle h, uint32_t** words, int32_t* rows);
+uhsdr_status uhsdr_cwgen_set_stream(uhsdr_cwgen_handle h, void* stream);
+uhsdr_status uhsdr_cwgen_synchronize(uhsdr_cwgen_handle h);
+uhsdr_status uhsdr_cwgen_destroy(uhsdr_cwgen_handle h);
 
 /* Digital-mode tap of the RX chain: tap = device f32 [C][N/4], written by every following
    uhsdr_rx_process with a_buffer[0] after biquad_1, the sample the firmware hands its modems

@@ -234,6 +234,31 @@ def main():
                           "hbm_frac": round(C * N * per / ms / 1e6 / HBM_PEAK_GBS, 4),
                           "finite": bool(torch.isfinite(a0).all().item()) and bool((iq != 0).any().item())})
             tx.close()
+    if "c4txcw" in want:
+        # CW transmit at the C4 SSB-TX shape: one kernel (tx_cw), an iambic B keyer at 30 wpm with texts in
+        # rotation, every fifth channel squeezed by hand and every sixth idle.  Beside the SSB-TX line
+        # of the same process when both are asked for (--only c4tx,c4txcw)
+        C, N = 262144 // 8, 256
+        s = torch.cuda.current_stream()
+        texts = [b"CQ CQ DE UHSDR K", b"5NN TU 73", b"the quick brown fox", b"QRZ? PSE AGN", b"", b""]
+        tx = U.TxChain(U.default_tx_config(dmod_mode=U.DEMOD_CW, cw_keyer_speed=30), channels=C, frames=N, stream=s.cuda_stream)
+        tx.set_cw_keyer(capacity=64, echo_capacity=64)
+        keys = torch.zeros((C, N // 32), dtype=torch.uint8, device="cuda")
+        keys[4::6] = 3
+        tx.cw_keys(keys)
+        tx.cw_put_text([texts[c % 6] for c in range(C)])
+        iq = torch.empty((C, N, 2), dtype=torch.int32, device="cuda")
+        a0 = torch.empty((C, N), dtype=torch.float32, device="cuda")
+        ms = time_calls(lambda: tx.process_cw(iq, a0), a.steps, a.warmup)
+        # 8 B I/Q frame out and the 4 B a0 copy; a key byte and a flag byte per 32 frames; the keyer's
+        # 11 words and the queue's counters once per call
+        per = 8 + 4 + 2 / 32 + 2 * 4 * 15 / N
+        lines.append({"workload": "C4 per-GPU share: CW-TX (iambic B keyer 30 wpm, tone, envelope, final I/Q stage; one kernel)",
+                      "precision": "exact", "channels": C, "frames_per_call": N, "pipelined": False, "ms_per_call": round(ms, 4),
+                      "msamples_per_s": round(C * N / ms / 1e3, 1), "alg_bytes_per_frame": round(per, 2),
+                      "hbm_frac": round(C * N * per / ms / 1e6 / HBM_PEAK_GBS, 4),
+                      "finite": bool(torch.isfinite(a0).all().item()) and bool((iq != 0).any().item())})
+        tx.close()
     if "c5" in want:
         C, N = 1048576 // 8, 256
         cfg = U.default_config(filter_path=4, dmod_mode=U.DEMOD_CW)

@@ -25,3 +25,4 @@ from .cwdec import CwDecoder  # noqa: F401
 from .rtty import RttyDecoder  # noqa: F401
 from .psk import PskDecoder  # noqa: F401
 from .digimod import RttyModulator, PskModulator  # noqa: F401
+from .cwgen import CwGenerator  # noqa: F401

@@ -111,7 +111,9 @@ class TxConfig(C.Structure):
         ("treble_gain", C.c_int32), ("filter_disable", C.c_int32), ("power_factor", C.c_float),
         ("gain_i", C.c_float), ("gain_q", C.c_float), ("phase_balance", C.c_float),
         ("fm_deviation_5k", C.c_int32), ("fm_subaudible_tone", C.c_int32), ("fm_tone_burst_mode", C.c_int32),
-        ("digi_lsb", C.c_int32), ("reserved", C.c_int32 * 12),
+        ("digi_lsb", C.c_int32), ("cw_lsb", C.c_int32), ("cw_keyer_mode", C.c_int32), ("cw_keyer_speed", C.c_int32),
+        ("cw_keyer_weight", C.c_int32), ("cw_paddle_reverse", C.c_int32), ("cw_rx_delay", C.c_int32), ("cw_sidetone_freq", C.c_int32),
+        ("reserved", C.c_int32 * 5),
     ]
 
 
@@ -129,7 +131,9 @@ class TxPlan(C.Structure):
         ("fm_sub_on", C.c_int32), ("fm_sub_step", C.c_uint32), ("fm_sub_scale", C.c_float),
         ("dds_table", C.c_int16 * 1024), ("tune_step", C.c_uint32 * 2), ("tone_burst_step", C.c_uint32),
         ("tone_burst_scale", C.c_float), ("am", C.c_int32), ("digiq", C.c_int32), ("digiq_i_gain", C.c_float),
-        ("digiq_q_gain", C.c_float), ("reserved", C.c_int32 * 24),
+        ("digiq_q_gain", C.c_float), ("cw", C.c_int32), ("cw_keyer_mode", C.c_int32), ("cw_keyer_speed", C.c_int32),
+        ("cw_keyer_weight", C.c_int32), ("cw_paddle_reverse", C.c_int32), ("cw_rx_delay", C.c_int32), ("cw_sidetone_freq", C.c_int32),
+        ("reserved", C.c_int32 * 17),
     ]
 
 
@@ -293,6 +297,23 @@ SIGNATURES = {
     "uhsdr_pskmod_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "uhsdr_pskmod_create_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "uhsdr_pskmod_prepare_tx": (C.c_int, [C.c_void_p]),
+    "uhsdr_cwgen_create": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_cwgen_create_host": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "uhsdr_cwgen_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_cwgen_set_speed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_cwgen_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uhsdr_cwgen_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_cwgen_process_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_cwgen_outputs": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "uhsdr_cwgen_peek": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "uhsdr_cwgen_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_cwgen_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_cwgen_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uhsdr_tx_cw_set_speed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_tx_cw_outputs": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
 }
 # the calls uhsdr_rttymod_* and uhsdr_pskmod_* have in common
 for _m in ("rttymod", "pskmod"):
@@ -424,7 +445,7 @@ TX_ARG_MAP = {
     "comp": "comp_level", "txfilter": "tx_filter", "txbass": "bass_gain", "txtreble": "treble_gain",
     "txpwr": "power_factor", "txgi": "gain_i", "txgq": "gain_q", "txphase": "phase_balance",
     "fm5k": "fm_deviation_5k", "subtone": "fm_subaudible_tone", "burstmode": "fm_tone_burst_mode",
-    "txsrc": "audio_source", "digilsb": "digi_lsb",
+    "txsrc": "audio_source", "digilsb": "digi_lsb", "cwlsb": "cw_lsb",
 }
 FLAGS1_AM_TX_FILTER_DISABLE, FLAGS1_SSB_TX_FILTER_DISABLE = 0x08, 0x40   # hardware/uhsdr_board.h:513,516
 TUNE_OFF, TUNE_SINGLE, TUNE_TWO = range(3)      # uhsdr_tx_set_tune

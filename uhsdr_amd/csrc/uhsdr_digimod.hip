@@ -31,7 +31,7 @@
 #include <string.h>
 #include <new>
 
-#include "uhsdr_internal.h"
+#include "uhsdr_digimod_host.h"
 #include "uhsdr_psk.h"
 #include "uhsdr_rttymod.h"
 #include "uhsdr_pskmod.h"
@@ -136,22 +136,7 @@ __global__ __launch_bounds__(DM_WG) void digimod_ctl(DigiModArena a, typename M:
     if (c < a.C) dm_ctl_one<M>(a, p, c, op);
 }
 
-// the part of a handle both modulators have
-struct DigiMod
-{
-    DigiModArena a;
-    void* mem;           // one allocation behind the arena: the two tables, then the state
-    size_t bytes;
-    bool host;           // state in host memory
-    hipStream_t stream;
-    uint32_t t;          // samples since reset
-    // the producer's side of a device handle's queues, kept on the host: the put counters, the
-    // queues' bytes, and room for the consumed counters read back at a put
-    uint32_t* h_put;
-    uint32_t* h_consumed;
-    uint8_t* h_text;
-};
-
+// the part of a handle both modulators have: DigiMod, uhsdr_digimod_host.h
 struct uhsdr_rttymod_s : DigiMod { RttyModParams p; };
 struct uhsdr_pskmod_s : DigiMod { PskModParams p; };
 
@@ -300,7 +285,7 @@ static uhsdr_status dm_check_create(const char* who, int32_t num_channels, int32
 
 // Appends to every channel's queue what fits of its row.  The free space of a queue depends on what
 // the modulator has taken, so a device handle waits for the work enqueued and reads the counters back.
-static uhsdr_status dm_put_text(DigiMod* h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted)
+uhsdr_status dm_put_text(DigiMod* h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted)
 {
     if (!h || !text || !len) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
     const int32_t C = h->a.C;
@@ -384,7 +369,7 @@ static uhsdr_status dm_outputs(DigiMod* h, uint32_t** consumed, uint32_t** txoff
     return UHSDR_OK;
 }
 
-static uhsdr_status dm_set_stream(DigiMod* h, void* stream)
+uhsdr_status dm_set_stream(DigiMod* h, void* stream)
 {
     if (!h || h->host) { uhsdr_set_error("digimod: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
     // what is enqueued on the old stream reads and writes the state and the queues: the new
@@ -394,7 +379,7 @@ static uhsdr_status dm_set_stream(DigiMod* h, void* stream)
     return UHSDR_OK;
 }
 
-static uhsdr_status dm_synchronize(DigiMod* h)
+uhsdr_status dm_synchronize(DigiMod* h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
     if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));

@@ -587,6 +587,11 @@ void uhsdr_tx_config_default(uhsdr_tx_config* c)
     c->gain_i = 1.0f;
     c->gain_q = 1.0f;
     c->phase_balance = 0.0f;
+    c->cw_keyer_mode = 0;                        /* CW_KEYER_MODE_IAM_B */
+    c->cw_keyer_speed = 20;                      /* CW_KEYER_SPEED_DEFAULT */
+    c->cw_keyer_weight = 100;
+    c->cw_rx_delay = 8;
+    c->cw_sidetone_freq = 750;                   /* CW_SIDETONE_FREQ_DEFAULT */
 }
 
 /* AudioManagement_CalcTxCompLevel preset table, audio_management.c:250-265 */
@@ -600,11 +605,25 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
 {
     if (!cfg || !p) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
     const int fm = cfg->dmod_mode == UHSDR_DEMOD_FM, am = cfg->dmod_mode == UHSDR_DEMOD_AM;
-    const int digi = cfg->dmod_mode == UHSDR_DEMOD_DIGI;
-    if (cfg->dmod_mode != UHSDR_DEMOD_USB && cfg->dmod_mode != UHSDR_DEMOD_LSB && !fm && !am && !digi)
+    const int digi = cfg->dmod_mode == UHSDR_DEMOD_DIGI, cw = cfg->dmod_mode == UHSDR_DEMOD_CW;
+    if (cfg->dmod_mode != UHSDR_DEMOD_USB && cfg->dmod_mode != UHSDR_DEMOD_LSB && !fm && !am && !digi && !cw)
     {
-        uhsdr_set_error("transmit mode %d: SSB (USB/LSB), AM and FM voice and DIGI (RTTY / BPSK) are implemented", cfg->dmod_mode);
+        uhsdr_set_error("transmit mode %d: SSB (USB/LSB), AM and FM voice, DIGI (RTTY / BPSK) and CW are implemented", cfg->dmod_mode);
         return UHSDR_UNSUPPORTED;
+    }
+    if (cw && cfg->audio_source == UHSDR_TX_AUDIO_DIGIQ)
+    {
+        /* the firmware ignores the USB I/Q in CW (tx_processor.c:950-953); here it is refused */
+        uhsdr_set_error("CW transmit with the USB I/Q source");
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (cw && (cfg->cw_keyer_mode < 0 || cfg->cw_keyer_mode > 3 || cfg->cw_keyer_speed < 5 || cfg->cw_keyer_speed > 48 ||
+               cfg->cw_keyer_weight < 50 || cfg->cw_keyer_weight > 150 || cfg->cw_rx_delay < 0 || cfg->cw_rx_delay > 50 ||
+               cfg->cw_sidetone_freq < 400 || cfg->cw_sidetone_freq > 1000))
+    {
+        uhsdr_set_error("CW keyer: mode %d, speed %d, weight %d, rx_delay %d, sidetone %d not 0 .. 3, 5 .. 48, 50 .. 150, 0 .. 50, 400 .. 1000",
+                        cfg->cw_keyer_mode, cfg->cw_keyer_speed, cfg->cw_keyer_weight, cfg->cw_rx_delay, cfg->cw_sidetone_freq);
+        return UHSDR_ARGUMENT_ERROR;
     }
     if (digi && cfg->audio_source == UHSDR_TX_AUDIO_DIGIQ)
     {
@@ -638,7 +657,11 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
     memset(p, 0, sizeof *p);
     p->dmod_mode = cfg->dmod_mode;
     /* DIGI: TxProcessor_SSB(..., 0, ts.digi_lsb) (tx_processor.c:819, :842) */
-    p->lsb = digi ? cfg->digi_lsb != 0 : cfg->dmod_mode == UHSDR_DEMOD_LSB;
+    p->lsb = digi ? cfg->digi_lsb != 0 : cw ? cfg->cw_lsb != 0 : cfg->dmod_mode == UHSDR_DEMOD_LSB;
+    /* CW: TxProcessor_CW (tx_processor.c:856-888); the final stage runs with the digiq gains (iq_gain_comp 1.0) */
+    p->cw = cw;
+    p->cw_keyer_mode = cfg->cw_keyer_mode; p->cw_keyer_speed = cfg->cw_keyer_speed; p->cw_keyer_weight = cfg->cw_keyer_weight;
+    p->cw_paddle_reverse = cfg->cw_paddle_reverse != 0; p->cw_rx_delay = cfg->cw_rx_delay; p->cw_sidetone_freq = cfg->cw_sidetone_freq;
     p->audio_source = cfg->audio_source;
 
     /* TxProcessor_AudioBufferFill gain (tx_processor.c:354-381) */
@@ -704,7 +727,7 @@ uhsdr_status uhsdr_tx_plan_build(const uhsdr_tx_config* cfg, uhsdr_tx_plan* p)
     case UHSDR_IQ_CONV_M12KHZ: p->freq_shift_hz = -12000; break;
     default: p->freq_shift_hz = 0; break;
     }
-    if (digi) p->freq_shift_hz = 0;     /* the modulators' signal stays around the centre frequency */
+    if (digi || cw) p->freq_shift_hz = 0;     /* the modulators' and the keyer's signal stays around the centre frequency */
     if (p->freq_shift_hz != 0)
     {
         const int32_t conv = p->freq_shift_hz < 0 ? -p->freq_shift_hz : p->freq_shift_hz;

@@ -25,6 +25,7 @@
 #include <math.h>
 #include "uhsdr_internal.h"
 #include "uhsdr_dsp.h"
+#include "uhsdr_cwgen_host.h"
 
 #define TX_DELAY_SLOTS (UHSDR_TX_DELAY / BLK)   // 10 blocks of 32
 #define TX_T UHSDR_TX_HILBERT_TAPS
@@ -621,6 +622,100 @@ __global__ void __launch_bounds__(256) tx_digiq(const uhsdr_tx_plan* plan, const
     dst[k] = make_int4(tx_to_int32(I[0]), tx_to_int32(Q[0]), tx_to_int32(I[1]), tx_to_int32(Q[1]));
 }
 
+// CW transmit (TxProcessor_CW, tx_processor.c:856-888, and the final stage :282-330 with iq_gain_comp
+// 1.0), channel == lane as cwgen_gen (uhsdr_cwgen.hip): per 32-frame block the keyer once, then the
+// block's samples from its plan, the exchange of I and Q unless cw_lsb, a0, gains, phase balance and
+// the int32 DAC frames.  In TUNE the keyer stands still and the tone runs on the channel's accumulator.
+// The frames go through LDS tiles so that a row's 64 int32 (32 frames) leave as one 256-byte store:
+// lane l writes word l of the row, I from the first tile and Q from the second, which lies 16 words
+// further so that the 16 I and 16 Q words a half-wave reads fall on 32 different banks.
+struct TxCwArgs
+{
+    CwGenArena a;
+    CwGenParams p;
+    const uhsdr_tx_plan* plan;
+    const uint8_t* keys;
+    int* iq;
+    float* a0;
+    uint8_t* flags;
+    int blocks, ld, tune;
+    uint32_t tune_step;
+};
+
+constexpr int CW_PITCH = CWGEN_BLOCK + 1;
+
+__global__ void __launch_bounds__(64) tx_cw(TxCwArgs t)
+{
+    __shared__ int16_t sine[1024];
+    __shared__ float env[CWGEN_ENV_SIZE];
+    __shared__ int tile[2 * 64 * CW_PITCH + 16];
+    __shared__ float atile[64 * CW_PITCH];
+    const uhsdr_tx_plan* __restrict__ P = t.plan;
+    const CwGenArena& a = t.a;
+    const int lane = threadIdx.x, c0 = blockIdx.x * 64, c = c0 + lane;
+    const bool live = c < a.m.C;
+    const int rows = a.m.C - c0 < 64 ? a.m.C - c0 : 64;
+    {
+        const uint32_t* src = (const uint32_t*)a.m.sine;
+        uint32_t* dst = (uint32_t*)sine;
+        for (int i = lane; i < 512; i += 64) dst[i] = src[i];
+        for (int i = lane; i < CWGEN_ENV_SIZE; i += 64) env[i] = a.env[i];
+    }
+    int* const ti = tile;
+    int* const tq = tile + 64 * CW_PITCH + 16;
+    CwGenChan ch{};
+    if (live) ch.load(a, c);
+    __syncthreads();
+    const float gi = P->digiq_i_gain, gq = P->digiq_q_gain, ph = P->phase_balance;
+    const bool lsb = P->lsb != 0;
+    const uint32_t step = t.tune ? t.tune_step : t.p.step;
+    for (int b = 0; b < t.blocks; b++)
+    {
+        if (live)
+        {
+            const size_t kb = (size_t)c * t.blocks + b;             // c < C, b < blocks
+            CwGenBlock plan;
+            if (t.tune)
+            {
+                // ts.tune: softdds_runIQ on every block (tx_processor.c:865-870)
+                plan.flags = CWGEN_F_ACTIVE; plan.acc = ch.acc; plan.rise = -1; plan.fall = -1;
+                ch.acc += (uint32_t)CWGEN_BLOCK * step;
+            }
+            else plan = ch.block(a, t.p, c, t.keys[kb]);
+            t.flags[kb] = (uint8_t)plan.flags;
+            const bool on = (plan.flags & CWGEN_F_ACTIVE) != 0;
+            for (int s = 0; s < CWGEN_BLOCK; s++)
+            {
+                float si = 0.0f, sq = 0.0f;
+                if (on) cwgen_sample(plan, step, s, sine, env, si, sq);
+                float I = lsb ? si : sq, Q = lsb ? sq : si;
+                I = I * gi;
+                Q = Q * gq;
+                if (ph < 0) { const float e = I * ph; Q = Q + e; }
+                else if (ph > 0) { const float e = Q * ph; I = I + e; }
+                ti[lane * CW_PITCH + s] = tx_to_int32(I);
+                tq[lane * CW_PITCH + s] = tx_to_int32(Q);
+                atile[lane * CW_PITCH + s] = si;
+            }
+        }
+        __syncthreads();
+        {
+            int* dst = t.iq + ((size_t)c0 * t.ld + (size_t)b * CWGEN_BLOCK) * 2 + lane;      // frame 32 b + lane / 2 < N = ld, c0 + r < C
+            const int* src = ((lane & 1) ? tq : ti) + (lane >> 1);
+#pragma unroll 8
+            for (int r = 0; r < rows; r++) dst[(size_t)r * t.ld * 2] = src[r * CW_PITCH];
+            if (t.a0 && lane < CWGEN_BLOCK)
+            {
+                float* ad = t.a0 + (size_t)c0 * t.ld + (size_t)b * CWGEN_BLOCK + lane;
+#pragma unroll 8
+                for (int r = 0; r < rows; r++) ad[(size_t)r * t.ld] = atile[r * CW_PITCH + lane];
+            }
+        }
+        __syncthreads();
+    }
+    if (live) ch.store(a, c, t.p);
+}
+
 // ------------------------------------------------------------------------------------
 // host runtime
 
@@ -651,6 +746,9 @@ struct uhsdr_tx_s
     uhsdr_pskmod_handle pmod;
     int16_t* mod_row;
     float ssb_i_gain, ssb_q_gain;    // the plan's final gains with SSB_GAIN_COMP (RTTY); BPSK runs with iq_gain_comp 1.0
+    // CW transmit: the generator the handle owns and the key lines of the following calls [C][N/32]
+    uhsdr_cwgen_handle cw;
+    const uint8_t* cw_keys;
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
@@ -707,6 +805,7 @@ extern "C" uhsdr_status uhsdr_tx_reset(uhsdr_tx_handle h)
     h->calls_issued = 0;
     if (h->rmod) return uhsdr_rttymod_reset(h->rmod);
     if (h->pmod) return uhsdr_pskmod_reset(h->pmod);
+    if (h->cw) return uhsdr_cwgen_reset(h->cw);
     return UHSDR_OK;
 }
 
@@ -721,6 +820,12 @@ extern "C" uhsdr_status uhsdr_tx_set_tune(uhsdr_tx_handle h, int32_t tune)
     }
     // AudioManagement_SetSidetoneForDemodMode -> softdds_configRunIQ(freq, rate, smooth = 0): both
     // accumulators restart at 0, on entering and on leaving TUNE (audio_management.c:377-404)
+    if (h->plan.cw && h->cw)
+    {
+        // CW: the tone is the keyer's own oscillator, one accumulator per channel; ts.tune is a flag
+        // there, so the two-tone setting sends the single tone as well
+        HIPCHK(hipMemsetAsync(h->cw->a.is + (size_t)CWGEN_I_ACC * h->C, 0, sizeof(uint32_t) * (size_t)h->C, h->stream));
+    }
     h->tune = tune;
     h->tune_acc[0] = h->tune_acc[1] = 0;
     return UHSDR_OK;
@@ -803,9 +908,28 @@ extern "C" uhsdr_status uhsdr_tx_create(const uhsdr_tx_config* cfg, int32_t C, i
     return uhsdr_tx_reset(h);
 }
 
+// CW: one kernel on the handle's stream, whatever the pipelined and precision settings are
+static uhsdr_status tx_process_cw(uhsdr_tx_s* h, int32_t* iq, float* a0)
+{
+    if (!iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (!h->cw) { uhsdr_set_error("CW transmit without a keyer: uhsdr_tx_set_cw_keyer first"); return UHSDR_ARGUMENT_ERROR; }
+    if (!h->tune && !h->cw_keys) { uhsdr_set_error("CW transmit without key lines: uhsdr_tx_cw_keys first"); return UHSDR_ARGUMENT_ERROR; }
+    const int blocks = h->N / BLK;
+    const uhsdr_status fs = cg_flags_room(h->cw, blocks);
+    if (fs != UHSDR_OK) return fs;
+    TxCwArgs t;
+    t.a = h->cw->ca; t.p = h->cw->p; t.plan = h->d_plan; t.keys = h->cw_keys; t.iq = iq; t.a0 = a0; t.flags = h->cw->flags;
+    t.blocks = blocks; t.ld = h->N; t.tune = h->tune != 0; t.tune_step = h->plan.tune_step[0];
+    hipLaunchKernelGGL(tx_cw, dim3((h->C + 63) / 64), dim3(64), 0, h->stream, t);
+    HIPCHK(hipGetLastError());
+    h->calls_done += blocks;
+    return UHSDR_OK;
+}
+
 extern "C" uhsdr_status uhsdr_tx_process(uhsdr_tx_handle h, const int32_t* audio, int32_t* iq, float* a0)
 {
     const bool digi = h && h->plan.dmod_mode == UHSDR_DEMOD_DIGI;
+    if (h && h->plan.cw) return tx_process_cw(h, iq, a0);
     if (!h || (!audio && !digi) || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
     if (digi && !h->rmod && !h->pmod)
     {
@@ -968,6 +1092,59 @@ extern "C" uhsdr_status uhsdr_tx_set_psk_mod(uhsdr_tx_handle h, int32_t enable, 
     return UHSDR_OK;
 }
 
+// ---- CW transmit: the keyer inside the chain ----
+
+static uhsdr_status tx_check_cw(uhsdr_tx_handle h, bool need_keyer)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (!h->plan.cw) { uhsdr_set_error("not a CW transmit handle (dmod_mode %d)", h->plan.dmod_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (need_keyer && !h->cw) { uhsdr_set_error("no keyer: uhsdr_tx_set_cw_keyer first"); return UHSDR_ARGUMENT_ERROR; }
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_set_cw_keyer(uhsdr_tx_handle h, int32_t text_capacity, int32_t echo_capacity)
+{
+    uhsdr_status st = tx_check_cw(h, false);
+    if (st != UHSDR_OK) return st;
+    const uhsdr_tx_plan& P = h->plan;
+    const uhsdr_cwgen_config cfg = { P.cw_keyer_mode, P.cw_keyer_speed, P.cw_keyer_weight, P.cw_paddle_reverse, P.cw_rx_delay, P.cw_sidetone_freq };
+    uhsdr_cwgen_handle g = nullptr;
+    if ((st = uhsdr_cwgen_create(h->C, &cfg, text_capacity, echo_capacity, h->stream, &g)) != UHSDR_OK) return st;
+    if (h->cw)
+    {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)uhsdr_cwgen_destroy(h->cw);
+    }
+    h->cw = g;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_cw_keys(uhsdr_tx_handle h, const uint8_t* keys)
+{
+    const uhsdr_status st = tx_check_cw(h, false);
+    if (st != UHSDR_OK) return st;
+    h->cw_keys = keys;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_tx_cw_put_text(uhsdr_tx_handle h, const uint8_t* text, const int32_t* len, int32_t stride, int32_t* accepted)
+{
+    const uhsdr_status st = tx_check_cw(h, true);
+    return st != UHSDR_OK ? st : uhsdr_cwgen_put_text(h->cw, text, len, stride, accepted);
+}
+
+extern "C" uhsdr_status uhsdr_tx_cw_set_speed(uhsdr_tx_handle h, int32_t speed, int32_t weight)
+{
+    const uhsdr_status st = tx_check_cw(h, true);
+    return st != UHSDR_OK ? st : uhsdr_cwgen_set_speed(h->cw, speed, weight);
+}
+
+extern "C" uhsdr_status uhsdr_tx_cw_outputs(uhsdr_tx_handle h, uint8_t** flags, uint32_t** consumed, uint8_t** echo, uint32_t** echo_total, uint8_t** state)
+{
+    const uhsdr_status st = tx_check_cw(h, true);
+    return st != UHSDR_OK ? st : uhsdr_cwgen_outputs(h->cw, flags, consumed, echo, echo_total, state);
+}
+
 static uhsdr_status tx_check_mod(uhsdr_tx_handle h)
 {
     const uhsdr_status st = tx_check_digi(h);
@@ -1067,6 +1244,7 @@ extern "C" uhsdr_status uhsdr_tx_destroy(uhsdr_tx_handle h)
     }
     if (h->txa2) (void)hipFree(h->txa2);
     tx_drop_mod(h);
+    if (h->cw) (void)uhsdr_cwgen_destroy(h->cw);
     (void)hipFree(h->arena);
     (void)hipFree(h->d_plan);
     (void)hipFree(h->d_taps2);

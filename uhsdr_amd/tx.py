@@ -121,6 +121,59 @@ class TxChain:
         _abi.check(self.lib.uhsdr_tx_process(self.handle, None, C.c_void_p(iq.data_ptr()),
                                              C.c_void_p(a0.data_ptr() if a0 is not None else 0)), "uhsdr_tx_process")
 
+    # ---- CW transmit (dmod_mode DEMOD_CW): the keyer inside the chain ----
+
+    def set_cw_keyer(self, capacity: int = 128, echo_capacity: int = 256) -> None:
+        """the handle's CW generator with the config's keyer settings (uhsdr_tx_set_cw_keyer)"""
+        _abi.check(self.lib.uhsdr_tx_set_cw_keyer(self.handle, int(capacity), int(echo_capacity)), "uhsdr_tx_set_cw_keyer")
+        self._echo_capacity = int(echo_capacity)
+
+    def cw_keys(self, keys) -> None:
+        """keys: uint8 cuda tensor [C][frames / 32], read by the following process_cw calls; keep it alive"""
+        if keys is not None and (tuple(keys.shape) != (self.channels, self.frames // 32) or keys.element_size() != 1 or not keys.is_contiguous()):
+            raise ValueError("keys must be a contiguous uint8 tensor [C][frames / 32]")
+        self._keys = keys
+        _abi.check(self.lib.uhsdr_tx_cw_keys(self.handle, C.c_void_p(keys.data_ptr() if keys is not None else 0)), "uhsdr_tx_cw_keys")
+
+    def cw_put_text(self, text):
+        """text: one bytes object per channel (or one for all); returns the accepted counts int32 [C]"""
+        import numpy as np
+        if isinstance(text, (bytes, bytearray)):
+            text = [bytes(text)] * self.channels
+        if len(text) != self.channels:
+            raise ValueError("one text per channel")
+        length = np.array([len(t) for t in text], np.int32)
+        stride = max(1, int(length.max()))
+        rows = np.zeros((self.channels, stride), np.uint8)
+        for c, t in enumerate(text):
+            rows[c, :len(t)] = np.frombuffer(bytes(t), np.uint8)
+        accepted = np.zeros(self.channels, np.int32)
+        _abi.check(self.lib.uhsdr_tx_cw_put_text(self.handle, rows.ctypes.data_as(C.c_void_p), length.ctypes.data_as(C.c_void_p),
+                                                 stride, accepted.ctypes.data_as(C.c_void_p)), "uhsdr_tx_cw_put_text")
+        return accepted
+
+    def cw_set_speed(self, speed: int, weight: int = 100) -> None:
+        _abi.check(self.lib.uhsdr_tx_cw_set_speed(self.handle, int(speed), int(weight)), "uhsdr_tx_cw_set_speed")
+
+    def cw_outputs(self):
+        """(flags uint8 [C][frames / 32] of the last call, consumed uint32 [C], echo uint8 [C][echo_capacity], echo_total
+        uint32 [C], state uint8 [C]) as host arrays; the work enqueued must be complete"""
+        import numpy as np
+        p = [C.c_void_p() for _ in range(5)]
+        _abi.check(self.lib.uhsdr_tx_cw_outputs(self.handle, *(C.byref(x) for x in p)), "uhsdr_tx_cw_outputs")
+        shapes = ((self.channels, self.frames // 32), self.channels, (self.channels, self._echo_capacity), self.channels, self.channels)
+        out = []
+        for ptr, shape, dtype in zip(p, shapes, (np.uint8, np.uint32, np.uint8, np.uint32, np.uint8)):
+            arr = np.zeros(shape, dtype)
+            if ptr.value:
+                _abi.check(self.lib.uhsdr_copy_to_host(arr.ctypes.data_as(C.c_void_p), ptr, arr.nbytes), "uhsdr_copy_to_host")
+            out.append(arr)
+        return tuple(out)
+
+    def process_cw(self, iq, a0=None) -> None:
+        """uhsdr_tx_process on a CW handle: no audio input"""
+        self.process_digi(iq, a0)
+
     def close(self) -> None:
         if self.handle:
             self.lib.uhsdr_tx_destroy(self.handle)
