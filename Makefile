@@ -2,7 +2,7 @@
 #
 #   make            -> uhsdr_amd/lib/libuhsdr_amd.so   (product: C-ABI, HIP kernels + host setup)
 #                      oracle/build/libuhsdr_oracle.so (test infrastructure: CPU restatement)
-#                      tests/build/libuhsdr_libm_probe{,_host}.so (test-only libm probes)
+#                      tests/build/libuhsdr_libm_probe{,_host}.so, libuhsdr_expf_probe{,_host}.so (test-only libm probes)
 #   make ref        -> oracle/_ref/uhsdr_ref          (reference firmware chain, needs /root/reference)
 #
 # Host C is compiled without FP contraction and without -march, like the reference build,
@@ -20,10 +20,10 @@ ORACLE  := oracle/build/libuhsdr_oracle.so
 OBJDIR  := uhsdr_amd/build
 
 HOST_SRCS := uhsdr_amd/csrc/uhsdr_setup.c uhsdr_amd/csrc/uhsdr_filter_tables.c
-HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip
+HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip uhsdr_amd/csrc/uhsdr_nr.hip
 HOST_OBJS := $(patsubst uhsdr_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRCS))
 HIP_OBJS  := $(patsubst uhsdr_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
-HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h
+HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h uhsdr_amd/csrc/uhsdr_nr.h uhsdr_amd/csrc/uhsdr_nr_tables.h uhsdr_amd/csrc/uhsdr_libm_expf.h
 
 EXAMPLE := examples/build/rx_batch
 
@@ -31,8 +31,11 @@ EXAMPLE := examples/build/rx_batch
 # build under exactly the product's HIPFLAGS, the host build under exactly HOSTCFLAGS
 PROBE      := tests/build/libuhsdr_libm_probe.so
 PROBE_HOST := tests/build/libuhsdr_libm_probe_host.so
+# the same pair for ul_expf (tests/test_expf.py, tests/test_gpu_expf.py)
+EXPF_PROBE      := tests/build/libuhsdr_expf_probe.so
+EXPF_PROBE_HOST := tests/build/libuhsdr_expf_probe_host.so
 
-all: $(LIB) $(CMSISLIB) $(ORACLE) $(EXAMPLE) $(PROBE) $(PROBE_HOST)
+all: $(LIB) $(CMSISLIB) $(ORACLE) $(EXAMPLE) $(PROBE) $(PROBE_HOST) $(EXPF_PROBE) $(EXPF_PROBE_HOST)
 
 $(OBJDIR) uhsdr_amd/lib oracle/build tests/build:
 	mkdir -p $@
@@ -41,6 +44,12 @@ $(PROBE): tests/device/libm_probe.hip uhsdr_amd/csrc/uhsdr_libm.h | tests/build
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 
 $(PROBE_HOST): tests/device/libm_probe_host.c uhsdr_amd/csrc/uhsdr_libm.h | tests/build
+	$(CC) $(HOSTCFLAGS) -shared -o $@ $< -lm
+
+$(EXPF_PROBE): tests/device/expf_probe.hip uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_libm_expf.h | tests/build
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+
+$(EXPF_PROBE_HOST): tests/device/expf_probe_host.c uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_libm_expf.h | tests/build
 	$(CC) $(HOSTCFLAGS) -shared -o $@ $< -lm
 
 $(OBJDIR)/%.o: uhsdr_amd/csrc/%.c $(HDRS) | $(OBJDIR)

@@ -980,6 +980,82 @@ uhsdr_status uhsdr_cwgen_set_stream(uhsdr_cwgen_handle h, void* stream);
 uhsdr_status uhsdr_cwgen_synchronize(uhsdr_cwgen_handle h);
 uhsdr_status uhsdr_cwgen_destroy(uhsdr_cwgen_handle h);
 
+/* ---- Spectral noise reduction: 12 / 6 ksps audio in, the same audio with the noise reduced ----
+ * The firmware's spectral_noise_reduction_3 (drivers/audio/audio_nr.c:1841-2195), one instance per
+ * channel: half-overlapping 256-sample frames under a square-root Hann window, arm_cfft_f32, an MMSE
+ * noise estimate with a speech-presence probability, the Ephraim-Malah gain inside the filter's
+ * pass band, a smoothing of the gains over NN bins against musical noise, the inverse transform,
+ * the window again and overlap-add.  Exact to the reference: the same binary32 output at every
+ * sample and the same NN in every frame, with the double-precision intermediates where the C
+ * promotes to double.  The settings are handle-wide, as ts and nr_params are one per transceiver:
+ *   alpha                 nr_params.alpha, 0 .. 1 (uhsdr_nr_alpha_from_strength: the firmware's
+ *                         0.799 + nr_strength / 1000.0)
+ *   asnr                  NR2.asnr 2 .. 30 dB, default 30
+ *   width                 NR2.width 1 .. 5, default 4: NN is at most 1 + 2 * width
+ *   power_threshold_int   NR2.power_threshold_int 10 .. 100, default 40
+ *   width_hz, offset_hz   FilterInfo[ts.filters_p->id].width and ts.filters_p->offset, 0 .. 65535:
+ *                         the pass band whose bins [VAD_low, VAD_high) are weighted
+ *   sample_rate           6000 (nr_params.NR_decimation_active) or 12000, the rate of the frames;
+ *                         uhsdr_nr_process decides it as the firmware does and ignores this field
+ * create and reset leave every channel as a fresh noise reduction (every static zero, first_time 1):
+ * the first 20 frames pass unchanged while the noise floor is averaged.
+ * process_frames: in, out = f32 [C][stride], `frames` frames of 128 samples each per row, frames *
+ * 128 <= stride, device memory (host memory for process_frames_host), stream-ordered; in and out
+ * must not overlap.  A frame's output is the overlap-add of its first half with the frame before,
+ * so it lags the input by 128 samples.
+ * process: the 12 ksps stream around it, AudioDriver_RxProcessorNoiseReduction (audio_driver.c:
+ * 2328-2434): below a filter width of 2701 Hz the 4-tap 2:1 decimator in front and the 40-tap 1:2
+ * interpolator with the factor 2.0 behind; 128-sample frames are collected, and their results come
+ * out after the output FIFO's latency of two frames (silence until then).  The firmware runs the
+ * frame stage in its main loop; here that loop never falls behind (AudioNr_HandleNoiseReduction
+ * after every block).  n: samples per row, a multiple of 8 (the firmware's block of 32 codec frames
+ * at 12 ksps), n <= stride; anything else is UHSDR_LENGTH_ERROR.  in and out must not overlap here
+ * either: the input is read again after the output is written.  A handle is used either through
+ * process_frames or through process from a reset on.
+ * state: per channel, into host arrays of num_channels (null: not wanted), after everything
+ * enqueued: first_time (1 fresh, 2 averaging, 3 running), NN of the last frame and its power_ratio.
+ * Reference oddities kept: the upper half is weighted at bin 255 - b, not 256 - b; the smoothing's
+ * upper-edge loop overwrites part of the middle loop's result; a negative lower band edge wraps
+ * through uint8_t to VAD_low 126, an empty band in which nothing is weighted; a restart keeps no
+ * state here, while the firmware keeps its last overlap half.  The smoothing loops index relative to
+ * the band and leave the firmware's arrays for a narrow or extreme one: a configuration is refused
+ * with UHSDR_ARGUMENT_ERROR unless, for M = 1 + 2 * width, VAD_high >= 2 M - 1 and VAD_low + M / 2
+ * + M - 2 <= 127 (width 4: VAD_high >= 17, VAD_low <= 116), or the band is empty.  A frame whose
+ * band holds no power has a NaN power_ratio, which the C converts to int (undefined); here that
+ * frame has NN = 1.
+ * Not built: the noise blanker (alt_noise_blanking), the LMS noise reduction, the #if 0 notch code,
+ * the noise reduction inside the RX chain. */
+typedef struct uhsdr_nr_config
+{
+    float   alpha;
+    int32_t asnr, width, power_threshold_int;
+    int32_t width_hz, offset_hz;
+    int32_t sample_rate;
+    int32_t reserved[9];
+} uhsdr_nr_config;
+typedef struct uhsdr_nr_s* uhsdr_nr_handle;
+
+void         uhsdr_nr_config_default(uhsdr_nr_config* cfg);
+float        uhsdr_nr_alpha_from_strength(int32_t nr_strength);
+/* VAD_low and VAD_high of a configuration, or the status uhsdr_nr_create would give */
+uhsdr_status uhsdr_nr_band(const uhsdr_nr_config* cfg, int32_t* vad_low, int32_t* vad_high);
+uhsdr_status uhsdr_nr_create(int32_t num_channels, const uhsdr_nr_config* cfg, void* stream, uhsdr_nr_handle* out);
+/* the same noise reduction with its state in host memory, for the _host calls (no device call) */
+uhsdr_status uhsdr_nr_create_host(int32_t num_channels, const uhsdr_nr_config* cfg, uhsdr_nr_handle* out);
+uhsdr_status uhsdr_nr_reset(uhsdr_nr_handle h);
+uhsdr_status uhsdr_nr_set_stream(uhsdr_nr_handle h, void* stream);
+uhsdr_status uhsdr_nr_process_frames(uhsdr_nr_handle h, const float* in, float* out, int32_t frames, int32_t stride);
+uhsdr_status uhsdr_nr_process_frames_host(uhsdr_nr_handle h, const float* in, float* out, int32_t frames, int32_t stride);
+uhsdr_status uhsdr_nr_process(uhsdr_nr_handle h, const float* in, float* out, int32_t n, int32_t stride);
+uhsdr_status uhsdr_nr_process_host(uhsdr_nr_handle h, const float* in, float* out, int32_t n, int32_t stride);
+uhsdr_status uhsdr_nr_state(uhsdr_nr_handle h, int32_t* first_time, int32_t* nn, float* power_ratio);
+uhsdr_status uhsdr_nr_synchronize(uhsdr_nr_handle h);
+uhsdr_status uhsdr_nr_destroy(uhsdr_nr_handle h);
+/* For tests and diagnosis only, not for the signal path (it builds its tables on every call):
+   arm_cfft_f32(&arm_cfft_sR_f32_len256, x, inverse, 1) on 256 interleaved complex values in host
+   memory, the transform of the host twin (tests/test_icfft_host.py pins it against the reference) */
+uhsdr_status uhsdr_nr_cfft256_host(float* x, int32_t inverse);
+
 /* Digital-mode tap of the RX chain: tap = device f32 [C][N/4], written by every following
    uhsdr_rx_process with a_buffer[0] after biquad_1, the sample the firmware hands its modems
    (audio_driver.c:2537-2557); null turns it off.  Available where the firmware runs them: a 12 ksps

@@ -5,13 +5,15 @@
  *   libm_check asin <stride>     every stride-th float in [-1, 1] (and NaN operands past it)
  *   libm_check atan2x1 <stride>  every stride-th binary32 y (all signs) against atan2f(y, 1.0f)
  *   libm_check atanpos <stride>  ul_atanf_pos (atan2f's reduction) on every stride-th float in [0, inf]
+ *   libm_check expf <stride>     every stride-th binary32 x (all signs, infinities and NaNs); stride 1
+ *                                is all 2^32 operands (tests/golden/expf_pin.txt holds that run's count)
  * Prints mismatches (first 10) and a summary line; exit status 1 on any mismatch. */
 #define _GNU_SOURCE
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
-#include "../uhsdr_amd/csrc/uhsdr_libm.h"
+#include "../uhsdr_amd/csrc/uhsdr_libm_expf.h"
 
 static uint64_t rng = 0x9E3779B97F4A7C15ull;
 static uint32_t next32(void) { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (uint32_t)(rng >> 16); }
@@ -70,6 +72,22 @@ int main(int argc, char** argv)
             }
         }
         printf("atanf(a >= 0): %ld of %ld arguments differ\n", bad, n);
+    }
+    else if (!strcmp(argv[1], "expf"))
+    {
+        const long stride = atol(argv[2]);
+        float (*volatile g_expf)(float) = expf;      /* libm's entry point, never folded */
+        for (uint64_t u = 0; u <= 0xffffffffull; u += stride)
+        {
+            const float x = ul_asfloat((uint32_t)u);
+            const float r0 = g_expf(x), r1 = ul_expf(x);
+            ++n;
+            if (ul_asuint(r0) != ul_asuint(r1))
+            {
+                if (bad++ < 10) printf("expf(%a): glibc %a (%08x), ours %a (%08x)\n", x, r0, ul_asuint(r0), r1, ul_asuint(r1));
+            }
+        }
+        printf("expf: %ld of %ld arguments differ\n", bad, n);
     }
     else if (!strcmp(argv[1], "atan2x1"))
     {

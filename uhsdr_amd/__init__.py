@@ -7,7 +7,7 @@ from ._abi import (RxConfig, RxPlan, build_plan, plan_supported, plan_fma_ok, co
                    DEMOD_USB, DEMOD_LSB, DEMOD_CW, DEMOD_AM, DEMOD_SAM, DEMOD_FM, DEMOD_DIGI,
                    DEMOD_SSBSTEREO, DEMOD_IQ, SAM_SIDEBAND_BOTH, SAM_SIDEBAND_LSB, SAM_SIDEBAND_USB,
                    SAM_SIDEBAND_STEREO, DSP_NOTCH_ENABLE, BOARD_OVI40, BOARD_MCHF,
-                   UHSDR_OK, UHSDR_ARGUMENT_ERROR, UHSDR_UNSUPPORTED, UHSDR_TIMEOUT, UhsdrError,
+                   UHSDR_OK, UHSDR_ARGUMENT_ERROR, UHSDR_LENGTH_ERROR, UHSDR_UNSUPPORTED, UHSDR_TIMEOUT, UhsdrError,
                    PRECISION_EXACT, PRECISION_FMA,
                    SCHEDULE_AUTO, SCHEDULE_SPLIT_PIPE, SCHEDULE_SPLIT_FUSED, SCHEDULE_CHAIN, ADC_CLIP, ADC_HALF_CLIP, ADC_QUARTER_CLIP,
                    TWINPEAKS_SAMPLING, TWINPEAKS_DONE, TWINPEAKS_WAIT, TWINPEAKS_UNCORRECTABLE,
@@ -26,3 +26,4 @@ from .rtty import RttyDecoder  # noqa: F401
 from .psk import PskDecoder  # noqa: F401
 from .digimod import RttyModulator, PskModulator  # noqa: F401
 from .cwgen import CwGenerator  # noqa: F401
+from .nr import NrProcessor, nr_config, nr_band  # noqa: F401

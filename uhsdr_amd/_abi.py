@@ -166,6 +166,13 @@ class SpectrumPlan(C.Structure):
     ]
 
 
+class NrConfig(C.Structure):
+    _fields_ = [
+        ("alpha", C.c_float), ("asnr", C.c_int32), ("width", C.c_int32), ("power_threshold_int", C.c_int32),
+        ("width_hz", C.c_int32), ("offset_hz", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 9),
+    ]
+
+
 # every exported entry point of include/uhsdr.h: name -> (restype, argtypes)
 SIGNATURES = {
     "uhsdr_rx_config_default": (None, [C.POINTER(RxConfig)]),
@@ -309,6 +316,21 @@ SIGNATURES = {
     "uhsdr_cwgen_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_cwgen_synchronize": (C.c_int, [C.c_void_p]),
     "uhsdr_cwgen_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_nr_config_default": (None, [C.POINTER(NrConfig)]),
+    "uhsdr_nr_alpha_from_strength": (C.c_float, [C.c_int32]),
+    "uhsdr_nr_band": (C.c_int, [C.POINTER(NrConfig), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "uhsdr_nr_create": (C.c_int, [C.c_int32, C.POINTER(NrConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_nr_create_host": (C.c_int, [C.c_int32, C.POINTER(NrConfig), C.POINTER(C.c_void_p)]),
+    "uhsdr_nr_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_nr_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_nr_process_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nr_process_frames_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nr_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nr_process_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nr_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhsdr_nr_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_nr_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_nr_cfft256_host": (C.c_int, [C.c_void_p, C.c_int32]),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -222,4 +222,175 @@ __device__ __forceinline__ void cfft_core(float2 (&z)[SpecGeom<L>::K], float2* X
     }
 }
 
+// arm_cfft_f32(S, p, 1, 1) for fft_len 256 (arm_cfft_f32.c:583-627): the imaginary parts negated,
+// the same transform, and after the bit reversal re *= invL, im = -(im) * invL.  The scaling is per
+// element, so it is applied here to the butterfly results y[0][k] (position 8 * lane + k, lanes
+// 0..31); the caller's bit reversal moves the scaled values.
+__device__ __forceinline__ void icfft256_core(float2 (&z)[4], float2* X, const float* __restrict__ tw,
+                                              const float* __restrict__ twl, int lane, float2 (&y)[1][8])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) z[k].y = -z[k].y;
+    cfft_core<256>(z, X, tw, twl, lane, y);
+    const float invL = 1.0f / 256.0f;
+    if (lane < SpecGeom<256>::NBF)
+    {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) y[0][k] = make_float2(y[0][k].x * invL, -(y[0][k].y) * invL);
+    }
+}
+
+// ---- host restatement of arm_cfft_f32 for fft_len 256, forward and inverse, for the host twins
+// (uhsdr_nr_process_frames_host): the reference's loops over an interleaved complex array, with
+// the twiddles and the bit-reversal swap pairs of a uhsdr_spectrum_plan built for 256 points ----
+
+// 8-point DFT core of arm_radix8_butterfly_f32 on x[2 * (base + k * stride)], k = 0..7; tstep 0:
+// the twiddle-free first group
+static inline void cfft_host_radix8(float* x, int base, int stride, const float* tw, int tstep)
+{
+    const float C81 = 0.70710678118f;
+    float re[8], im[8], sr[4], dr[4], si[4], di[4], Xr[8], Xi[8];
+    for (int k = 0; k < 8; k++)
+    {
+        re[k] = x[2 * (base + k * stride)];
+        im[k] = x[2 * (base + k * stride) + 1];
+    }
+    for (int k = 0; k < 4; k++)
+    {
+        sr[k] = re[k] + re[k + 4];
+        dr[k] = re[k] - re[k + 4];
+        si[k] = im[k] + im[k + 4];
+        di[k] = im[k] - im[k + 4];
+    }
+    const float a = sr[0] - sr[2], b = sr[0] + sr[2], cc = sr[1] - sr[3], d = sr[1] + sr[3];
+    const float ai = si[0] - si[2], bi = si[0] + si[2], ci = si[1] - si[3], dd = si[1] + si[3];
+    Xr[0] = b + d;   Xi[0] = bi + dd;
+    Xr[4] = b - d;   Xi[4] = bi - dd;
+    Xr[2] = a + ci;  Xi[2] = ai - cc;
+    Xr[6] = a - ci;  Xi[6] = ai + cc;
+    const float u = (dr[1] - dr[3]) * C81, v = (dr[1] + dr[3]) * C81;
+    const float ui = (di[1] - di[3]) * C81, vi = (di[1] + di[3]) * C81;
+    const float e0 = dr[0] - u, e1 = dr[0] + u, f0 = dr[2] - v, f1 = dr[2] + v;
+    const float g0 = di[0] - ui, g1 = di[0] + ui, h0 = di[2] - vi, h1 = di[2] + vi;
+    Xr[1] = e1 + h1; Xi[1] = g1 - f1;
+    Xr[7] = e1 - h1; Xi[7] = g1 + f1;
+    Xr[5] = e0 + h0; Xi[5] = g0 - f0;
+    Xr[3] = e0 - h0; Xi[3] = g0 + f0;
+    for (int k = 0; k < 8; k++)
+    {
+        float yr = Xr[k], yi = Xi[k];
+        if (tstep && k)
+        {
+            const float c = tw[2 * k * tstep], s = tw[2 * k * tstep + 1];
+            const float p1 = c * Xr[k], p2 = s * Xi[k], p3 = c * Xi[k], p4 = s * Xr[k];
+            yr = p1 + p2;
+            yi = p3 - p4;
+        }
+        x[2 * (base + k * stride)] = yr;
+        x[2 * (base + k * stride) + 1] = yi;
+    }
+}
+
+static inline void cfft_host_rot(float* y, float xr, float xi, float c, float s)
+{
+    const float m0 = xr * c, m1 = xi * s, m2 = xi * c, m3 = xr * s;
+    y[0] = m0 + m1;
+    y[1] = m2 - m3;
+}
+
+// x: 256 interleaved complex values, transformed in place as arm_cfft_f32(&arm_cfft_sR_f32_len256,
+// x, inverse, 1) does
+static inline void cfft256_host(const uhsdr_spectrum_plan* p, float* x, int inverse)
+{
+    constexpr int L = 256, Q = L / 4;
+    const float* tw = p->twiddle;
+    if (inverse)
+        for (int l = 0; l < L; l++) x[2 * l + 1] = -x[2 * l + 1];
+    // arm_cfft_radix8by4_f32 (arm_cfft_f32.c:319-557): top rows t = 0 .. Q/2 (t = 0 untwiddled,
+    // t = Q/2 the MIDDLE block), then the bottom rows Q - t with the mirrored twiddles of t
+    float *c1 = x, *c2 = x + 2 * Q, *c3 = x + 4 * Q, *c4 = x + 6 * Q;
+    for (int t = 0; t <= Q / 2; t++)
+    {
+        float *p1 = c1 + 2 * t, *p2 = c2 + 2 * t, *p3 = c3 + 2 * t, *p4 = c4 + 2 * t;
+        const float s13r = p1[0] + p3[0], d13r = p1[0] - p3[0];
+        const float s13i = p1[1] + p3[1], d13i = p1[1] - p3[1];
+        const float t2r = d13r + p2[1] - p4[1], t2i = d13i - p2[0] + p4[0];
+        const float t3r = s13r - p2[0] - p4[0], t3i = s13i - p2[1] - p4[1];
+        const float t4r = d13r - p2[1] + p4[1], t4i = d13i + p2[0] - p4[0];
+        p1[0] = s13r + p2[0] + p4[0];
+        p1[1] = s13i + p2[1] + p4[1];
+        if (t == 0)
+        {
+            p2[0] = t2r; p2[1] = t2i;
+            p3[0] = t3r; p3[1] = t3i;
+            p4[0] = t4r; p4[1] = t4i;
+            continue;
+        }
+        cfft_host_rot(p2, t2r, t2i, tw[2 * t], tw[2 * t + 1]);
+        cfft_host_rot(p3, t3r, t3i, tw[4 * t], tw[4 * t + 1]);
+        cfft_host_rot(p4, t4r, t4i, tw[6 * t], tw[6 * t + 1]);
+    }
+    for (int t = 1; t < Q / 2; t++)
+    {
+        const int b = Q - t;
+        float *p1 = c1 + 2 * b, *p2 = c2 + 2 * b, *p3 = c3 + 2 * b, *p4 = c4 + 2 * b;
+        const float s13r = p1[0] + p3[0], d13r = p1[0] - p3[0];
+        const float s13i = p1[1] + p3[1], d13i = p1[1] - p3[1];
+        const float u2r = p2[1] - p4[1] + d13r;
+        const float u2i = p1[1] - p3[1] - p2[0] + p4[0];
+        const float u3r = s13r - p2[0] - p4[0];
+        const float u3i = s13i - p2[1] - p4[1];
+        const float u4r = p2[1] - p4[1] - d13r;
+        const float u4i = p4[0] - p2[0] - d13i;
+        p1[1] = s13i + p2[1] + p4[1];
+        p1[0] = s13r + p2[0] + p4[0];
+        {
+            const float c = tw[2 * t], s = tw[2 * t + 1];
+            const float m0 = u2i * s, m1 = u2r * c, m2 = u2r * s, m3 = u2i * c;
+            p2[1] = m0 - m1;
+            p2[0] = m2 + m3;
+        }
+        {
+            const float c = tw[4 * t], s = tw[4 * t + 1];
+            const float m0 = -u3i * c, m1 = u3r * s, m2 = u3r * c, m3 = u3i * s;
+            p3[1] = m0 - m1;
+            p3[0] = m3 - m2;
+        }
+        {
+            const float c = tw[6 * t], s = tw[6 * t + 1];
+            const float m0 = u4i * s, m1 = u4r * c, m2 = u4r * s, m3 = u4i * c;
+            p4[1] = m0 - m1;
+            p4[0] = m2 + m3;
+        }
+    }
+    // arm_radix8_butterfly_f32 on each quarter, twiddle modifier 4
+    for (int k = 0; k < 4; k++)
+    {
+        float* q = x + 2 * k * Q;
+        int tm = 4;
+        for (int span = Q; span >= 8; span >>= 3, tm <<= 3)
+        {
+            const int stride = span >> 3;
+            for (int j = 0; j < stride; j++)
+                for (int g = j; g < Q; g += span) cfft_host_radix8(q, g, stride, tw, j * tm);
+        }
+    }
+    // arm_bitreversal_32: swap the complex values at the byte offsets of each table pair
+    for (int k = 0; k + 1 < p->bitrev_len; k += 2)
+    {
+        const int a = p->bitrev[k] >> 2, b = p->bitrev[k + 1] >> 2;
+        float t = x[a]; x[a] = x[b]; x[b] = t;
+        t = x[a + 1]; x[a + 1] = x[b + 1]; x[b + 1] = t;
+    }
+    if (inverse)
+    {
+        const float invL = 1.0f / (float)L;
+        for (int l = 0; l < L; l++)
+        {
+            x[2 * l] *= invL;
+            x[2 * l + 1] = -(x[2 * l + 1]) * invL;
+        }
+    }
+}
+
 #endif /* UHSDR_CFFT_H */

@@ -697,3 +697,40 @@ def psk_chain_fixture(path: str) -> dict:
     g["iq"] = iq
     g["speed"] = int(g["speed_idx"])
     return g
+
+
+def nr_audio(nsamples: int, rate: float = 6000.0, snr_db: float = 10.0, seed: int = 0, amplitude: float = 3000.0,
+             f0: float = 130.0, tone: float = 700.0, floor: float = 1.0, segment: float = 0.4) -> np.ndarray:
+    """float32 audio at the noise reduction's input (post-AGC amplitude), `rate` 6000 or 12000: a
+    repeating sequence of four segments of `segment` seconds -- a voiced signal (harmonics of `f0` up
+    to 2.4 kHz falling with 1 / k under a 5 Hz syllable envelope), a gap, a keyed CW `tone`
+    (60 ms dots), a gap -- plus white noise (counter-based, `seed`) `snr_db` below the voiced
+    signal's RMS.  In the gaps only the noise and a constant noise floor of `floor` sigma remain."""
+    t = np.arange(nsamples) / rate
+    seg = np.floor(t / segment).astype(np.int64) % 4
+    k = np.arange(1, int(2400.0 / f0) + 1)
+    voiced = (np.sin(2.0 * np.pi * f0 * t[:, None] * k[None, :]) / k[None, :]).sum(axis=1)
+    voiced *= 0.5 - 0.5 * np.cos(2.0 * np.pi * 5.0 * t)
+    cw = np.sin(2.0 * np.pi * tone * t) * (np.floor(t / 0.06).astype(np.int64) % 2 == 0)
+    rms = np.sqrt(np.mean(voiced ** 2)) if nsamples else 1.0
+    s = amplitude * (np.where(seg == 0, voiced / max(rms, 1e-12), 0.0) + np.where(seg == 2, cw, 0.0))
+    sigma = amplitude * 10.0 ** (-snr_db / 20.0)
+    ni, nq = _noise(np.array([3 << 16 | seed], np.int64), 0, nsamples, 1.0)
+    return (s + sigma * ni[0] + floor * nq[0]).astype(np.float32)
+
+
+def nr_fixture(path: str) -> dict:
+    """A recorded noise-reduction case (an npz of tools/nr/make_nr_golden.py) with its input
+    regenerated from the recorded arguments of nr_audio and checked against the recorded crc32: the
+    file's arrays plus `audio` (float32, read-only) and `cfg` (the configuration as a dict)."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    audio = nr_audio(**json.loads(str(g["gen"])))
+    if len(audio) != int(g["samples"]) or zlib.crc32(audio.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    audio.setflags(write=False)
+    g["audio"] = audio
+    g["cfg"] = json.loads(str(g["config"]))
+    return g
