@@ -9,14 +9,10 @@
 // common case, neighbouring channels keyed alike or idle -- touch one 256-byte line, and a lane that
 // does not costs one dword access, where a [C][256] layout would cost a line per lane always.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
-#include "uhsdr_internal.h"
+#include "uhsdr_arena.h"
 #include "uhsdr_cwdec.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int CWDEC_WG = 64;
 
@@ -28,125 +24,86 @@ __global__ __launch_bounds__(CWDEC_WG) void cw_decode(CwDecArena a, const uint8_
     cwdec_run_channel(a, c, state + (size_t)c * stride, blocks, offset, step, blocksize, spikecancel);
 }
 
-struct uhsdr_cwdec_s
+struct uhsdr_cwdec_s : ArenaMem
 {
     CwDecArena a;
-    void* mem;           // one allocation behind the arena
-    size_t bytes;
-    bool host;           // state in host memory (uhsdr_cwdec_create_host)
     int blocksize, spikecancel;
-    hipStream_t stream;
 };
-
-static size_t cwdec_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 static size_t cwdec_layout(CwDecArena& a, char* base)
 {
     const size_t C = (size_t)a.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += cwdec_align(n); return p; };   // null base: size only
-    a.ring = (uint32_t*)take(sizeof(uint32_t) * CWDEC_SIG_SIZE * C);
-    a.data = (uint32_t*)take(sizeof(uint32_t) * CWDEC_DATA_SIZE * C);
-    a.iscal = (int32_t*)take(sizeof(int32_t) * CWD_I_COUNT * C);
-    a.fscal = (float*)take(sizeof(float) * CWD_F_COUNT * C);
-    a.total = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.text = (uint8_t*)take(C * (size_t)a.text_capacity);
-    a.wpm = (uint8_t*)take(C);
-    return off;
-}
-
-static uhsdr_status cwdec_check(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity, const void* out)
-{
-    if (!out || num_channels < 1) { uhsdr_set_error("cwdec: bad argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (blocksize < 8 || blocksize > 128) { uhsdr_set_error("cwdec: blocksize %d not 8 .. 128", blocksize); return UHSDR_ARGUMENT_ERROR; }
-    if (spikecancel < 0 || spikecancel > 2) { uhsdr_set_error("cwdec: spikecancel %d not 0 .. 2", spikecancel); return UHSDR_ARGUMENT_ERROR; }
-    if (text_capacity < 8) { uhsdr_set_error("cwdec: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
-    return UHSDR_OK;
-}
-
-static uhsdr_cwdec_s* cwdec_new(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity, bool host)
-{
-    uhsdr_cwdec_s* h = new (std::nothrow) uhsdr_cwdec_s();
-    if (!h) return nullptr;
-    h->a.C = num_channels;
-    h->a.text_capacity = text_capacity;
-    h->blocksize = blocksize;
-    h->spikecancel = spikecancel;
-    h->host = host;
-    h->bytes = cwdec_layout(h->a, nullptr);
-    return h;
+    ArenaCarver m{base, 0};
+    a.ring = m.take<uint32_t>(CWDEC_SIG_SIZE * C);
+    a.data = m.take<uint32_t>(CWDEC_DATA_SIZE * C);
+    a.iscal = m.take<int32_t>(CWD_I_COUNT * C);
+    a.fscal = m.take<float>(CWD_F_COUNT * C);
+    a.total = m.take<uint32_t>(C);
+    a.text = m.take<uint8_t>(C * (size_t)a.text_capacity);
+    a.wpm = m.take<uint8_t>(C);
+    return m.off;
 }
 
 // every static of the firmware's decoder starts at zero
 extern "C" uhsdr_status uhsdr_cwdec_reset(uhsdr_cwdec_handle h)
 {
     if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
-    if (h->host) memset(h->mem, 0, h->bytes);
-    else HIPCHK(hipMemsetAsync(h->mem, 0, h->bytes, h->stream));
+    return h->zero_state();
+}
+
+static uhsdr_status cwdec_create(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity, bool host, void* stream,
+                                 uhsdr_cwdec_handle* out)
+{
+    if (!out || num_channels < 1) { uhsdr_set_error("cwdec: bad argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (blocksize < 8 || blocksize > 128) { uhsdr_set_error("cwdec: blocksize %d not 8 .. 128", blocksize); return UHSDR_ARGUMENT_ERROR; }
+    if (spikecancel < 0 || spikecancel > 2) { uhsdr_set_error("cwdec: spikecancel %d not 0 .. 2", spikecancel); return UHSDR_ARGUMENT_ERROR; }
+    if (text_capacity < 8) { uhsdr_set_error("cwdec: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_cwdec_s* h = new (std::nothrow) uhsdr_cwdec_s();
+    if (!h) return UHSDR_DEVICE_ERROR;
+    h->a.C = num_channels;
+    h->a.text_capacity = text_capacity;
+    h->blocksize = blocksize;
+    h->spikecancel = spikecancel;
+    h->host = host;
+    h->stream = (hipStream_t)stream;
+    h->bytes = cwdec_layout(h->a, nullptr);
+    uhsdr_status st = h->alloc("cwdec");
+    if (st == UHSDR_OK)
+    {
+        cwdec_layout(h->a, (char*)h->mem);
+        st = h->zero_state();
+    }
+    if (st != UHSDR_OK) { uhsdr_cwdec_destroy(h); return st; }
+    *out = h;
     return UHSDR_OK;
 }
 
 extern "C" uhsdr_status uhsdr_cwdec_create(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity,
                                            void* stream, uhsdr_cwdec_handle* out)
 {
-    const uhsdr_status st = cwdec_check(num_channels, blocksize, spikecancel, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_cwdec_s* h = cwdec_new(num_channels, blocksize, spikecancel, text_capacity, false);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->stream = (hipStream_t)stream;
-    const hipError_t e = hipMalloc(&h->mem, h->bytes);
-    if (e != hipSuccess)
-    {
-        uhsdr_set_error("cwdec: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-        delete h;
-        return UHSDR_DEVICE_ERROR;
-    }
-    cwdec_layout(h->a, (char*)h->mem);
-    const uhsdr_status rs = uhsdr_cwdec_reset(h);
-    if (rs != UHSDR_OK) { (void)hipFree(h->mem); delete h; return rs; }
-    *out = h;
-    return UHSDR_OK;
+    return cwdec_create(num_channels, blocksize, spikecancel, text_capacity, false, stream, out);
 }
 
 extern "C" uhsdr_status uhsdr_cwdec_create_host(int32_t num_channels, int32_t blocksize, int32_t spikecancel, int32_t text_capacity,
                                                 uhsdr_cwdec_handle* out)
 {
-    const uhsdr_status st = cwdec_check(num_channels, blocksize, spikecancel, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_cwdec_s* h = cwdec_new(num_channels, blocksize, spikecancel, text_capacity, true);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->mem = calloc(1, h->bytes);
-    if (!h->mem) { uhsdr_set_error("cwdec: host allocation of %zu bytes failed", h->bytes); delete h; return UHSDR_DEVICE_ERROR; }
-    cwdec_layout(h->a, (char*)h->mem);
-    *out = h;
-    return UHSDR_OK;
+    return cwdec_create(num_channels, blocksize, spikecancel, text_capacity, true, nullptr, out);
 }
 
 extern "C" uhsdr_status uhsdr_cwdec_destroy(uhsdr_cwdec_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (h->host) free(h->mem);
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-    }
+    h->release();
     delete h;
     return UHSDR_OK;
 }
 
-extern "C" uhsdr_status uhsdr_cwdec_set_stream(uhsdr_cwdec_handle h, void* stream)
-{
-    if (!h || h->host) { uhsdr_set_error("cwdec: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
-    h->stream = (hipStream_t)stream;
-    return UHSDR_OK;
-}
+extern "C" uhsdr_status uhsdr_cwdec_set_stream(uhsdr_cwdec_handle h, void* stream) { return arena_set_stream(h, "cwdec", stream, false); }
 
 static uhsdr_status cwdec_check_run(uhsdr_cwdec_handle h, const uint8_t* state, int32_t blocks, int64_t span, int32_t stride)
 {
     if (!h || !state) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (blocks < 0 || stride < 0 || span > stride) { uhsdr_set_error("cwdec: %d blocks do not fit a row of %d", blocks, stride); return UHSDR_LENGTH_ERROR; }
-    return UHSDR_OK;
+    return arena_check_row("cwdec", "blocks", blocks, span, stride);
 }
 
 // block b of a channel is state[c * stride + offset + b * step] (the RX chain's signal row holds one
@@ -156,7 +113,7 @@ uhsdr_status uhsdr_cwdec_launch(uhsdr_cwdec_handle h, const uint8_t* state, int3
     if (offset < 0 || step < 1) { uhsdr_set_error("cwdec: bad offset / step"); return UHSDR_ARGUMENT_ERROR; }
     const uhsdr_status st = cwdec_check_run(h, state, blocks, blocks ? (int64_t)offset + (int64_t)(blocks - 1) * step + 1 : 0, stride);
     if (st != UHSDR_OK) return st;
-    if (h->host) { uhsdr_set_error("cwdec: host handle, use uhsdr_cwdec_process_host"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, false, "cwdec", "uhsdr_cwdec_process_host")) return UHSDR_ARGUMENT_ERROR;
     if (blocks == 0) return UHSDR_OK;
     const int grid = (h->a.C + CWDEC_WG - 1) / CWDEC_WG;
     hipLaunchKernelGGL(cw_decode, dim3(grid), dim3(CWDEC_WG), 0, h->stream, h->a, state, blocks, stride, offset, step,
@@ -174,7 +131,7 @@ extern "C" uhsdr_status uhsdr_cwdec_process_host(uhsdr_cwdec_handle h, const uin
 {
     const uhsdr_status st = cwdec_check_run(h, state, blocks, blocks, stride);
     if (st != UHSDR_OK) return st;
-    if (!h->host) { uhsdr_set_error("cwdec: device handle, use uhsdr_cwdec_process"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, true, "cwdec", "uhsdr_cwdec_process")) return UHSDR_ARGUMENT_ERROR;
     for (int32_t c = 0; c < h->a.C; c++)
         cwdec_run_channel(h->a, c, state + (size_t)c * stride, blocks, 0, 1, h->blocksize, h->spikecancel);
     return UHSDR_OK;
@@ -191,9 +148,7 @@ extern "C" uhsdr_status uhsdr_cwdec_outputs(uhsdr_cwdec_handle h, uint8_t** text
 
 extern "C" uhsdr_status uhsdr_cwdec_synchronize(uhsdr_cwdec_handle h)
 {
-    if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));
-    return UHSDR_OK;
+    return h ? h->synchronize() : UHSDR_ARGUMENT_ERROR;
 }
 
 extern "C" int32_t uhsdr_cwdec_char_id(uint32_t code) { return cwdec_char_id(code); }

@@ -32,14 +32,10 @@
 // Chosen and not measured: one block per tile and two barriers per block; key bytes and flag bytes read and written by their lanes, one byte per channel per block, 1/256 of
 // the sample traffic.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
 #include "uhsdr_cwgen_host.h"
 #include "uhsdr_cwgen_tables.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int CG_WG = 64;
 constexpr int CG_PITCH = CWGEN_BLOCK + 1;
@@ -103,30 +99,27 @@ __global__ __launch_bounds__(CG_WG) void cwgen_reset(CwGenArena a, CwGenParams p
     ch.store(a, c, p);
 }
 
-static size_t cg_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-static size_t cg_layout(uhsdr_cwgen_s* h, char* base, size_t* tables)
+static size_t cg_layout(uhsdr_cwgen_s* h, char* base)
 {
     CwGenArena& a = h->ca;
     const size_t C = (size_t)a.m.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += cg_align(n); return p; };     // null base: size only
-    a.m.sine = (const int16_t*)take(sizeof(int16_t) * CG_SINE);
-    a.m.codes = (const uint16_t*)take(sizeof(uint16_t) * CG_SEND);
-    a.env = (const float*)take(sizeof(float) * CWGEN_ENV_SIZE);
-    a.dec_code = (const uint32_t*)take(sizeof(uint32_t) * CWGEN_DEC_MAX);
-    a.dec_out = (const uint32_t*)take(sizeof(uint32_t) * CWGEN_DEC_MAX);
-    if (tables) *tables = off;
-    a.m.is = (uint32_t*)take(sizeof(uint32_t) * CWGEN_I_COUNT * C);
-    a.m.consumed = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.m.txoff_at = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.m.put = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.echo_total = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.m.state = (uint8_t*)take(C);
-    a.m.text = (uint8_t*)take(C * (size_t)a.m.text_capacity);
-    a.echo = (uint8_t*)take(C * (size_t)a.echo_capacity);
+    ArenaCarver m{base, 0};
+    a.m.sine = m.take<int16_t>(CG_SINE);
+    a.m.codes = m.take<uint16_t>(CG_SEND);
+    a.env = m.take<float>(CWGEN_ENV_SIZE);
+    a.dec_code = m.take<uint32_t>(CWGEN_DEC_MAX);
+    a.dec_out = m.take<uint32_t>(CWGEN_DEC_MAX);
+    h->tables = m.off;
+    a.m.is = m.take<uint32_t>(CWGEN_I_COUNT * C);
+    a.m.consumed = m.take<uint32_t>(C);
+    a.m.txoff_at = m.take<uint32_t>(C);
+    a.m.put = m.take<uint32_t>(C);
+    a.echo_total = m.take<uint32_t>(C);
+    a.m.state = m.take<uint8_t>(C);
+    a.m.text = m.take<uint8_t>(C * (size_t)a.m.text_capacity);
+    a.echo = m.take<uint8_t>(C * (size_t)a.echo_capacity);
     h->a = a.m;
-    return off;
+    return m.off;
 }
 
 // CwGen_ReverseCode: the elements in sending order, the first one lowest
@@ -161,16 +154,9 @@ static void cg_fill_tables(const uhsdr_cwgen_s* h, char* dst)
 
 static void cg_free(uhsdr_cwgen_s* h)
 {
-    if (h->host) { free(h->mem); free(h->flags); }
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-        (void)hipFree(h->flags);
-        free(h->h_put);
-        free(h->h_consumed);
-        free(h->h_text);
-    }
+    dm_free(h);
+    if (h->host) free(h->flags);
+    else (void)hipFree(h->flags);
     delete h;
 }
 
@@ -234,46 +220,16 @@ static uhsdr_status cwgen_new(int32_t num_channels, const uhsdr_cwgen_config* cf
     h->ca.dec_count = CWGEN_CHARS + CWGEN_SIGNS;
     h->host = host;
     h->stream = (hipStream_t)stream;
-    size_t tables = 0;
-    h->bytes = cg_layout(h, nullptr, &tables);
-    const size_t C = (size_t)num_channels;
-    if (host)
+    h->bytes = cg_layout(h, nullptr);
+    uhsdr_status st = h->alloc("cwgen");
+    if (st == UHSDR_OK)
     {
-        h->mem = calloc(1, h->bytes);
-        if (!h->mem) { uhsdr_set_error("cwgen: host allocation of %zu bytes failed", h->bytes); delete h; return UHSDR_DEVICE_ERROR; }
-        cg_layout(h, (char*)h->mem, nullptr);
-        cg_fill_tables(h, (char*)h->mem);
+        cg_layout(h, (char*)h->mem);
+        st = dm_alloc_queues(h, "cwgen");
     }
-    else
-    {
-        const hipError_t e = hipMalloc(&h->mem, h->bytes);
-        if (e != hipSuccess)
-        {
-            uhsdr_set_error("cwgen: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-            delete h;
-            return UHSDR_DEVICE_ERROR;
-        }
-        cg_layout(h, (char*)h->mem, nullptr);
-        h->h_put = (uint32_t*)calloc(C, sizeof(uint32_t));
-        h->h_consumed = (uint32_t*)calloc(C, sizeof(uint32_t));
-        h->h_text = (uint8_t*)calloc(C, (size_t)text_capacity);
-        char* img = (char*)calloc(1, tables);
-        hipError_t ce = hipErrorOutOfMemory;
-        if (h->h_put && h->h_consumed && h->h_text && img)
-        {
-            cg_fill_tables(h, img);
-            ce = hipMemcpy(h->mem, img, tables, hipMemcpyHostToDevice);
-        }
-        free(img);
-        if (ce != hipSuccess)
-        {
-            uhsdr_set_error("cwgen: table upload failed: %s", hipGetErrorString(ce));
-            cg_free(h);
-            return UHSDR_DEVICE_ERROR;
-        }
-    }
-    const uhsdr_status rs = uhsdr_cwgen_reset(h);
-    if (rs != UHSDR_OK) { cg_free(h); return rs; }
+    if (st == UHSDR_OK) st = h->upload_tables("cwgen", [h](char* image) { cg_fill_tables(h, image); });
+    if (st == UHSDR_OK) st = uhsdr_cwgen_reset(h);
+    if (st != UHSDR_OK) { cg_free(h); return st; }
     *out = h;
     return UHSDR_OK;
 }
@@ -330,9 +286,10 @@ uhsdr_status cg_flags_room(uhsdr_cwgen_s* h, int32_t blocks)
 static uhsdr_status cg_check_run(uhsdr_cwgen_s* h, const uint8_t* keys, const float* i, const float* q, int32_t n, int32_t stride, bool host)
 {
     if (!h || !keys || !i || !q) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (n < 0 || stride < 0 || n > stride) { uhsdr_set_error("cwgen: %d samples do not fit a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
+    const uhsdr_status st = arena_check_row("cwgen", "samples", n, n, stride);
+    if (st != UHSDR_OK) return st;
     if (n % CWGEN_BLOCK) { uhsdr_set_error("cwgen: %d samples are not a multiple of %d", n, CWGEN_BLOCK); return UHSDR_LENGTH_ERROR; }
-    if (h->host != host) { uhsdr_set_error(host ? "cwgen: device handle, use the _process call" : "cwgen: host handle, use the _process_host call"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, host, "cwgen", host ? "the _process call" : "the _process_host call")) return UHSDR_ARGUMENT_ERROR;
     return UHSDR_OK;
 }
 

@@ -27,16 +27,12 @@
 // alignment; a 64-sample tile (8448 bytes; 10496 bytes of LDS with the table, so LDS does not
 // limit occupancy before the wave slots do).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
 #include "uhsdr_digimod_host.h"
 #include "uhsdr_psk.h"
 #include "uhsdr_rttymod.h"
 #include "uhsdr_pskmod.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int DM_WG = 64;
 constexpr int DM_TILE = 64;
@@ -140,25 +136,22 @@ __global__ __launch_bounds__(DM_WG) void digimod_ctl(DigiModArena a, typename M:
 struct uhsdr_rttymod_s : DigiMod { RttyModParams p; };
 struct uhsdr_pskmod_s : DigiMod { PskModParams p; };
 
-static size_t dm_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 template <class M>
-static size_t dm_layout(DigiMod* h, char* base, size_t* tables)
+static size_t dm_layout(DigiMod* h, char* base)
 {
     DigiModArena& a = h->a;
     const size_t C = (size_t)a.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += dm_align(n); return p; };   // null base: size only
-    a.sine = (const int16_t*)take(sizeof(int16_t) * DM_SINE);
-    a.codes = (const uint16_t*)take(sizeof(uint16_t) * M::codes);
-    if (tables) *tables = off;
-    a.is = (uint32_t*)take(sizeof(uint32_t) * M::rows * C);
-    a.consumed = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.txoff_at = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.put = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.state = (uint8_t*)take(C);
-    a.text = (uint8_t*)take(C * (size_t)a.text_capacity);
-    return off;
+    ArenaCarver m{base, 0};
+    a.sine = m.take<int16_t>(DM_SINE);
+    a.codes = m.take<uint16_t>(M::codes);
+    h->tables = m.off;
+    a.is = m.take<uint32_t>(M::rows * C);
+    a.consumed = m.take<uint32_t>(C);
+    a.txoff_at = m.take<uint32_t>(C);
+    a.put = m.take<uint32_t>(C);
+    a.state = m.take<uint8_t>(C);
+    a.text = m.take<uint8_t>(C * (size_t)a.text_capacity);
+    return m.off;
 }
 
 static void dm_fill_codes(RttyMod, uint16_t* codes) { rttymod_fill_codes(codes); }
@@ -179,17 +172,24 @@ static void dm_fill_tables(const DigiMod* h, char* dst)
     dm_fill_codes(M(), (uint16_t*)(dst + ((const char*)h->a.codes - (const char*)h->a.sine)));
 }
 
-static void dm_free(DigiMod* h)
+uhsdr_status dm_alloc_queues(DigiMod* h, const char* who)
 {
-    if (h->host) free(h->mem);
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-        free(h->h_put);
-        free(h->h_consumed);
-        free(h->h_text);
-    }
+    if (h->host) return UHSDR_OK;
+    const size_t C = (size_t)h->a.C;
+    h->h_put = (uint32_t*)calloc(C, sizeof(uint32_t));
+    h->h_consumed = (uint32_t*)calloc(C, sizeof(uint32_t));
+    h->h_text = (uint8_t*)calloc(C, (size_t)h->a.text_capacity);
+    if (h->h_put && h->h_consumed && h->h_text) return UHSDR_OK;
+    uhsdr_set_error("%s: host allocation of the queues failed", who);
+    return UHSDR_DEVICE_ERROR;
+}
+
+void dm_free(DigiMod* h)
+{
+    h->release();
+    free(h->h_put);         // null in a host handle
+    free(h->h_consumed);
+    free(h->h_text);
 }
 
 template <class M, class H>
@@ -231,47 +231,16 @@ static uhsdr_status dm_create(H* h, int32_t num_channels, int32_t text_capacity,
     h->a.text_capacity = text_capacity;
     h->host = host;
     h->stream = (hipStream_t)stream;
-    size_t tables = 0;
-    h->bytes = dm_layout<M>(h, nullptr, &tables);
-    const size_t C = (size_t)num_channels;
-    if (host)
+    h->bytes = dm_layout<M>(h, nullptr);
+    uhsdr_status st = h->alloc("digimod");
+    if (st == UHSDR_OK)
     {
-        h->mem = calloc(1, h->bytes);
-        if (!h->mem) { uhsdr_set_error("digimod: host allocation of %zu bytes failed", h->bytes); delete h; return UHSDR_DEVICE_ERROR; }
-        dm_layout<M>(h, (char*)h->mem, nullptr);
-        dm_fill_tables<M>(h, (char*)h->mem);
+        dm_layout<M>(h, (char*)h->mem);
+        st = dm_alloc_queues(h, "digimod");
     }
-    else
-    {
-        const hipError_t e = hipMalloc(&h->mem, h->bytes);
-        if (e != hipSuccess)
-        {
-            uhsdr_set_error("digimod: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-            delete h;
-            return UHSDR_DEVICE_ERROR;
-        }
-        dm_layout<M>(h, (char*)h->mem, nullptr);
-        h->h_put = (uint32_t*)calloc(C, sizeof(uint32_t));
-        h->h_consumed = (uint32_t*)calloc(C, sizeof(uint32_t));
-        h->h_text = (uint8_t*)calloc(C, (size_t)text_capacity);
-        char* img = (char*)malloc(tables);
-        hipError_t ce = hipErrorOutOfMemory;
-        if (h->h_put && h->h_consumed && h->h_text && img)
-        {
-            dm_fill_tables<M>(h, img);
-            ce = hipMemcpy(h->mem, img, tables, hipMemcpyHostToDevice);
-        }
-        free(img);
-        if (ce != hipSuccess)
-        {
-            uhsdr_set_error("digimod: table upload failed: %s", hipGetErrorString(ce));
-            dm_free(h);
-            delete h;
-            return UHSDR_DEVICE_ERROR;
-        }
-    }
-    const uhsdr_status rs = dm_reset<M>(h);
-    if (rs != UHSDR_OK) { dm_free(h); delete h; return rs; }
+    if (st == UHSDR_OK) st = h->upload_tables("digimod", [h](char* image) { dm_fill_tables<M>(h, image); });
+    if (st == UHSDR_OK) st = dm_reset<M>(h);
+    if (st != UHSDR_OK) { dm_free(h); delete h; return st; }
     *out = h;
     return UHSDR_OK;
 }
@@ -325,8 +294,7 @@ uhsdr_status dm_put_text(DigiMod* h, const uint8_t* text, const int32_t* len, in
 static uhsdr_status dm_check_run(const DigiMod* h, const int16_t* audio, int32_t n, int32_t stride)
 {
     if (!h || !audio) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (n < 0 || stride < 0 || n > stride) { uhsdr_set_error("digimod: %d samples do not fit a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
-    return UHSDR_OK;
+    return arena_check_row("digimod", "samples", n, n, stride);
 }
 
 template <class M, class H, class K>
@@ -334,7 +302,7 @@ static uhsdr_status dm_process(H* h, K kernel, int16_t* audio, int32_t n, int32_
 {
     const uhsdr_status st = dm_check_run(h, audio, n, stride);
     if (st != UHSDR_OK) return st;
-    if (h->host) { uhsdr_set_error("digimod: host handle, use the _process_host call"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, false, "digimod", "the _process_host call")) return UHSDR_ARGUMENT_ERROR;
     if (n == 0) return UHSDR_OK;
     hipLaunchKernelGGL(kernel, dim3((h->a.C + DM_WG - 1) / DM_WG), dim3(DM_WG), 0, h->stream, h->a, h->p, h->t, audio, (int)n, (int)stride);
     HIPCHK(hipGetLastError());
@@ -347,7 +315,7 @@ static uhsdr_status dm_process_host(H* h, int16_t* audio, int32_t n, int32_t str
 {
     const uhsdr_status st = dm_check_run(h, audio, n, stride);
     if (st != UHSDR_OK) return st;
-    if (!h->host) { uhsdr_set_error("digimod: device handle, use the _process call"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, true, "digimod", "the _process call")) return UHSDR_ARGUMENT_ERROR;
     for (int32_t c = 0; c < h->a.C; c++)
     {
         typename M::Chan ch{};
@@ -366,23 +334,6 @@ static uhsdr_status dm_outputs(DigiMod* h, uint32_t** consumed, uint32_t** txoff
     if (consumed) *consumed = h->a.consumed;
     if (txoff_at) *txoff_at = h->a.txoff_at;
     if (state) *state = h->a.state;
-    return UHSDR_OK;
-}
-
-uhsdr_status dm_set_stream(DigiMod* h, void* stream)
-{
-    if (!h || h->host) { uhsdr_set_error("digimod: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
-    // what is enqueued on the old stream reads and writes the state and the queues: the new
-    // stream's work, and a put_text that waits for the new stream only, must come after it
-    if ((hipStream_t)stream != h->stream) HIPCHK(hipStreamSynchronize(h->stream));
-    h->stream = (hipStream_t)stream;
-    return UHSDR_OK;
-}
-
-uhsdr_status dm_synchronize(DigiMod* h)
-{
-    if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));
     return UHSDR_OK;
 }
 

@@ -18,16 +18,12 @@
 // overlap-added to the second half of the frame before.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
-#include "uhsdr_internal.h"
+#include "uhsdr_arena.h"
 #include "uhsdr_cfft.h"
 #include "uhsdr_nr.h"
 #include "uhsdr_nr_tables.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int NR_WAVES = 4;
 constexpr int NR_STATE_FLOATS = NR_F_COUNT * NR_BINS;
@@ -347,16 +343,13 @@ static void nr_frame_host(const uhsdr_spectrum_plan* plan, const float* window, 
     for (int i = 0; i < NR_BINS; i++) last_out[i] = buf[NR_FFT + 2 * i];
 }
 
-struct uhsdr_nr_s
+struct uhsdr_nr_s : ArenaMem               // one allocation: window, plan, coefficients, state
 {
     NrArena a;
     NrParams p;
     uhsdr_nr_config cfg;
     uhsdr_spectrum_plan* host_plan;     // the host twin's tables (and the upload's source)
-    void* mem;                          // one allocation: window, plan, state
-    size_t bytes, tables, floats_end;
-    bool host;
-    hipStream_t stream;
+    size_t floats_end;
     // the stream: positions common to all channels, and the call's work rows
     NrParams sp;                        // the frames' parameters at the rate the stream runs them
     uhsdr_status stream_status;         // of sp: UHSDR_OK, or why uhsdr_nr_process refuses
@@ -367,28 +360,25 @@ struct uhsdr_nr_s
     size_t work_row;                    // floats per row of each
 };
 
-static size_t nr_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 static size_t nr_layout(uhsdr_nr_s* h, char* base)
 {
     NrArena& a = h->a;
     const size_t C = (size_t)a.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += nr_align(n); return p; };   // null base: size only
-    a.window = (const float*)take(sizeof(float) * NR_FFT);
-    a.plan = (const uhsdr_spectrum_plan*)take(sizeof(uhsdr_spectrum_plan));
-    a.dec_coeffs = (const float*)take(sizeof(float) * NR_DEC_TAPS);
-    a.int_coeffs = (const float*)take(sizeof(float) * NR_INT_TAPS);
-    h->tables = off;
-    a.fs = (float*)take(sizeof(float) * NR_STATE_FLOATS * C);
-    a.dec_hist = (float*)take(sizeof(float) * 4 * C);
-    a.int_hist = (float*)take(sizeof(float) * NR_INT_PHASE * C);
-    a.pend = (float*)take(sizeof(float) * NR_BINS * C);
-    a.queue[0] = (float*)take(sizeof(float) * NR_QUEUE * C);
-    a.queue[1] = (float*)take(sizeof(float) * NR_QUEUE * C);
-    h->floats_end = off;                // the float state ends here: reset clears tables .. floats_end
-    a.is = (int32_t*)take(sizeof(int32_t) * NR_I_COUNT * C);
-    return off;
+    ArenaCarver m{base, 0};
+    a.window = m.take<float>(NR_FFT);
+    a.plan = m.take<uhsdr_spectrum_plan>(1);
+    a.dec_coeffs = m.take<float>(NR_DEC_TAPS);
+    a.int_coeffs = m.take<float>(NR_INT_TAPS);
+    h->tables = m.off;
+    a.fs = m.take<float>(NR_STATE_FLOATS * C);
+    a.dec_hist = m.take<float>(4 * C);
+    a.int_hist = m.take<float>(NR_INT_PHASE * C);
+    a.pend = m.take<float>(NR_BINS * C);
+    a.queue[0] = m.take<float>(NR_QUEUE * C);
+    a.queue[1] = m.take<float>(NR_QUEUE * C);
+    h->floats_end = m.off;              // the float state ends here: reset clears tables .. floats_end
+    a.is = m.take<int32_t>(NR_I_COUNT * C);
+    return m.off;
 }
 
 extern "C" void uhsdr_nr_config_default(uhsdr_nr_config* cfg)
@@ -483,7 +473,7 @@ static uhsdr_status nr_create(int32_t num_channels, const uhsdr_nr_config* cfg, 
 {
     if (!out || !cfg || num_channels < 1) { uhsdr_set_error("nr: bad argument"); return UHSDR_ARGUMENT_ERROR; }
     NrParams p;
-    const uhsdr_status st = nr_params(cfg, &p);
+    uhsdr_status st = nr_params(cfg, &p);
     if (st != UHSDR_OK) return st;
     uhsdr_nr_s* h = new (std::nothrow) uhsdr_nr_s();
     if (!h) { uhsdr_set_error("nr: host allocation of the handle failed"); return UHSDR_DEVICE_ERROR; }
@@ -502,55 +492,28 @@ static uhsdr_status nr_create(int32_t num_channels, const uhsdr_nr_config* cfg, 
     uhsdr_spectrum_config sc;
     uhsdr_spectrum_config_default(&sc);
     sc.fft_len = NR_FFT;
+    st = UHSDR_DEVICE_ERROR;
     if (!h->host_plan) uhsdr_set_error("nr: host allocation of %zu bytes failed", sizeof(uhsdr_spectrum_plan));
-    if (!h->host_plan || uhsdr_spectrum_plan_build(&sc, h->host_plan) != UHSDR_OK)      // (plan_build sets its own error text)
+    else if (uhsdr_spectrum_plan_build(&sc, h->host_plan) == UHSDR_OK) st = h->alloc("nr");     // (plan_build sets its own error text)
+    if (st == UHSDR_OK)
     {
-        free(h->host_plan);
-        delete h;
-        return UHSDR_DEVICE_ERROR;
-    }
-    if (host)
-    {
-        h->mem = calloc(1, h->bytes);
-        if (!h->mem) { uhsdr_set_error("nr: host allocation of %zu bytes failed", h->bytes); free(h->host_plan); delete h; return UHSDR_DEVICE_ERROR; }
+        // the four tables go up one by one, so what lies between them in device memory is what hipMalloc left
         nr_layout(h, (char*)h->mem);
-        memcpy((void*)h->a.window, uhsdr_nr_sqrt_hann_256, sizeof(float) * NR_FFT);
-        memcpy((void*)h->a.plan, h->host_plan, sizeof(uhsdr_spectrum_plan));
-        memcpy((void*)h->a.dec_coeffs, uhsdr_nr_decimate_coeffs, sizeof(float) * NR_DEC_TAPS);
-        memcpy((void*)h->a.int_coeffs, uhsdr_nr_interpolate_coeffs, sizeof(float) * NR_INT_TAPS);
-    }
-    else
-    {
-        hipError_t e = hipMalloc(&h->mem, h->bytes);
-        if (e != hipSuccess)
+        const struct { const void *dst, *src; size_t n; } tab[4] = {
+            { h->a.window, uhsdr_nr_sqrt_hann_256, sizeof(float) * NR_FFT },
+            { h->a.plan, h->host_plan, sizeof(uhsdr_spectrum_plan) },
+            { h->a.dec_coeffs, uhsdr_nr_decimate_coeffs, sizeof(float) * NR_DEC_TAPS },
+            { h->a.int_coeffs, uhsdr_nr_interpolate_coeffs, sizeof(float) * NR_INT_TAPS } };
+        hipError_t e = hipSuccess;
+        for (int t = 0; t < 4 && e == hipSuccess; t++)
         {
-            uhsdr_set_error("nr: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-            free(h->host_plan);
-            delete h;
-            return UHSDR_DEVICE_ERROR;
+            if (host) memcpy((void*)tab[t].dst, tab[t].src, tab[t].n);
+            else e = hipMemcpy((void*)tab[t].dst, tab[t].src, tab[t].n, hipMemcpyHostToDevice);
         }
-        nr_layout(h, (char*)h->mem);
-        e = hipMemcpy((void*)h->a.window, uhsdr_nr_sqrt_hann_256, sizeof(float) * NR_FFT, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy((void*)h->a.plan, h->host_plan, sizeof(uhsdr_spectrum_plan), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy((void*)h->a.dec_coeffs, uhsdr_nr_decimate_coeffs, sizeof(float) * NR_DEC_TAPS, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy((void*)h->a.int_coeffs, uhsdr_nr_interpolate_coeffs, sizeof(float) * NR_INT_TAPS, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-        {
-            uhsdr_set_error("nr: table upload failed: %s", hipGetErrorString(e));
-            (void)hipFree(h->mem);
-            free(h->host_plan);
-            delete h;
-            return UHSDR_DEVICE_ERROR;
-        }
+        if (e != hipSuccess) { uhsdr_set_error("nr: table upload failed: %s", hipGetErrorString(e)); st = UHSDR_DEVICE_ERROR; }
     }
-    const uhsdr_status rs = uhsdr_nr_reset(h);
-    if (rs != UHSDR_OK)
-    {
-        if (host) free(h->mem); else (void)hipFree(h->mem);
-        free(h->host_plan);
-        delete h;
-        return rs;
-    }
+    if (st == UHSDR_OK) st = uhsdr_nr_reset(h);
+    if (st != UHSDR_OK) { uhsdr_nr_destroy(h); return st; }
     *out = h;
     return UHSDR_OK;
 }
@@ -568,28 +531,15 @@ extern "C" uhsdr_status uhsdr_nr_create_host(int32_t num_channels, const uhsdr_n
 extern "C" uhsdr_status uhsdr_nr_destroy(uhsdr_nr_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (h->host)
-    {
-        free(h->mem);
-        free(h->work);
-    }
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-        if (h->work) (void)hipFree(h->work);
-    }
+    h->release();
+    if (h->host) free(h->work);
+    else if (h->work) (void)hipFree(h->work);
     free(h->host_plan);
     delete h;
     return UHSDR_OK;
 }
 
-extern "C" uhsdr_status uhsdr_nr_set_stream(uhsdr_nr_handle h, void* stream)
-{
-    if (!h || h->host) { uhsdr_set_error("nr: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
-    h->stream = (hipStream_t)stream;
-    return UHSDR_OK;
-}
+extern "C" uhsdr_status uhsdr_nr_set_stream(uhsdr_nr_handle h, void* stream) { return arena_set_stream(h, "nr", stream, false); }
 
 static uhsdr_status nr_check_run(uhsdr_nr_handle h, const float* in, float* out, int32_t frames, int32_t stride)
 {
@@ -603,7 +553,7 @@ extern "C" uhsdr_status uhsdr_nr_process_frames(uhsdr_nr_handle h, const float* 
 {
     const uhsdr_status st = nr_check_run(h, in, out, frames, stride);
     if (st != UHSDR_OK) return st;
-    if (h->host) { uhsdr_set_error("nr: host handle, use uhsdr_nr_process_frames_host"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, false, "nr", "uhsdr_nr_process_frames_host")) return UHSDR_ARGUMENT_ERROR;
     if (frames == 0) return UHSDR_OK;
     const int grid = (h->a.C + NR_WAVES - 1) / NR_WAVES;
     hipLaunchKernelGGL(nr_frames, dim3(grid), dim3(NR_WAVES * 64), 0, h->stream, h->a, h->p, in, out, frames, stride);
@@ -615,7 +565,7 @@ extern "C" uhsdr_status uhsdr_nr_process_frames_host(uhsdr_nr_handle h, const fl
 {
     const uhsdr_status st = nr_check_run(h, in, out, frames, stride);
     if (st != UHSDR_OK) return st;
-    if (!h->host) { uhsdr_set_error("nr: device handle, use uhsdr_nr_process_frames"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, true, "nr", "uhsdr_nr_process_frames")) return UHSDR_ARGUMENT_ERROR;
     for (int32_t c = 0; c < h->a.C; c++)
         for (int32_t f = 0; f < frames; f++)
             nr_frame_host(h->a.plan, h->a.window, &h->p, h->a.fs + (size_t)c * NR_STATE_FLOATS, h->a.is + (size_t)c * NR_I_COUNT,
@@ -702,7 +652,7 @@ static uhsdr_status nr_stream_call(uhsdr_nr_handle h, const float* in, float* ou
     if (!h || !in || !out) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
     if (n < 0 || stride < 0 || n > stride || n % 8 != 0)
     { uhsdr_set_error("nr: %d samples: a multiple of 8 that fits a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
-    if (h->host != host) { uhsdr_set_error(host ? "nr: device handle, use uhsdr_nr_process" : "nr: host handle, use uhsdr_nr_process_host"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, host, "nr", host ? "uhsdr_nr_process" : "uhsdr_nr_process_host")) return UHSDR_ARGUMENT_ERROR;
     if (h->stream_status != UHSDR_OK)
     { uhsdr_set_error("nr: the band at the stream's frame rate (%d) is refused", h->decimated ? 6000 : 12000); return h->stream_status; }
     k->decimated = h->decimated;
@@ -795,9 +745,7 @@ extern "C" uhsdr_status uhsdr_nr_process_host(uhsdr_nr_handle h, const float* in
 
 extern "C" uhsdr_status uhsdr_nr_synchronize(uhsdr_nr_handle h)
 {
-    if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));
-    return UHSDR_OK;
+    return h ? h->synchronize() : UHSDR_ARGUMENT_ERROR;
 }
 
 extern "C" uhsdr_status uhsdr_nr_state(uhsdr_nr_handle h, int32_t* first_time, int32_t* nn, float* power_ratio)

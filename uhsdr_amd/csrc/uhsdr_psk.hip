@@ -23,14 +23,10 @@
 // before the current sample's arithmetic (it is never the slot the sample writes), so the read's
 // latency is not on the recursion's path.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
-#include "uhsdr_internal.h"
+#include "uhsdr_arena.h"
 #include "uhsdr_psk.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int PSK_WG = 64;
 constexpr int PSK_TILE = 32;
@@ -122,33 +118,27 @@ __global__ __launch_bounds__(PSK_WG) void psk_decode(PskArena a, PskParams p, Ps
     }
 }
 
-struct uhsdr_psk_s
+struct uhsdr_psk_s : ArenaMem
 {
     PskArena a;
     PskParams p;
     PskClock k;          // advanced on the host as the launches are enqueued
-    void* mem;           // one allocation behind the arena: the two tables, then the state
-    size_t bytes, tables;
-    bool host;           // state in host memory (uhsdr_psk_create_host)
-    hipStream_t stream;
 };
 
-static size_t psk_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
+// the two tables, then the state
 static size_t psk_layout(uhsdr_psk_s* h, char* base)
 {
     PskArena& a = h->a;
     const size_t C = (size_t)a.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += psk_align(n); return p; };   // null base: size only
-    a.sine = (const float*)take(sizeof(float) * 1024);
-    a.chars = (const uint8_t*)take(PSK_CODES);
-    h->tables = off;
-    a.fs = (float*)take(sizeof(float) * PSK_F_COUNT * C);
-    a.is = (uint32_t*)take(sizeof(uint32_t) * PSK_I_COUNT * C);
-    a.total = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.text = (uint8_t*)take(C * (size_t)a.text_capacity);
-    return off;
+    ArenaCarver m{base, 0};
+    a.sine = m.take<float>(1024);
+    a.chars = m.take<uint8_t>(PSK_CODES);
+    h->tables = m.off;
+    a.fs = m.take<float>(PSK_F_COUNT * C);
+    a.is = m.take<uint32_t>(PSK_I_COUNT * C);
+    a.total = m.take<uint32_t>(C);
+    a.text = m.take<uint8_t>(C * (size_t)a.text_capacity);
+    return m.off;
 }
 
 // the oscillator's table as floats and the varicode lookup, as they lie at the head of the arena
@@ -159,107 +149,65 @@ static void psk_fill_tables(const uhsdr_psk_s* h, char* dst)
     psk_fill_chars((uint8_t*)(dst + ((const char*)h->a.chars - (const char*)h->a.sine)));
 }
 
-static uhsdr_status psk_check(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, const void* out)
-{
-    if (!out || num_channels < 1) { uhsdr_set_error("psk: bad argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (speed_idx < 0 || speed_idx >= PSK_SPEED_COUNT) { uhsdr_set_error("psk: speed_idx %d not 0 .. 2", speed_idx); return UHSDR_ARGUMENT_ERROR; }
-    if (text_capacity < 8) { uhsdr_set_error("psk: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
-    return UHSDR_OK;
-}
-
-static uhsdr_psk_s* psk_new(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, bool host)
-{
-    uhsdr_psk_s* h = new (std::nothrow) uhsdr_psk_s();
-    if (!h) return nullptr;
-    h->a.C = num_channels;
-    h->a.text_capacity = text_capacity;
-    h->p = psk_params(speed_idx);
-    h->host = host;
-    h->bytes = psk_layout(h, nullptr);
-    return h;
-}
-
 // every static of the firmware's decoder starts at zero; the tables stay
 extern "C" uhsdr_status uhsdr_psk_reset(uhsdr_psk_handle h)
 {
     if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
-    char* state = (char*)h->mem + h->tables;
-    if (h->host) memset(state, 0, h->bytes - h->tables);
-    else HIPCHK(hipMemsetAsync(state, 0, h->bytes - h->tables, h->stream));
+    const uhsdr_status st = h->zero_state();
+    if (st != UHSDR_OK) return st;
     h->k = PskClock{};
+    return UHSDR_OK;
+}
+
+static uhsdr_status psk_create(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, bool host, void* stream, uhsdr_psk_handle* out)
+{
+    if (!out || num_channels < 1) { uhsdr_set_error("psk: bad argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (speed_idx < 0 || speed_idx >= PSK_SPEED_COUNT) { uhsdr_set_error("psk: speed_idx %d not 0 .. 2", speed_idx); return UHSDR_ARGUMENT_ERROR; }
+    if (text_capacity < 8) { uhsdr_set_error("psk: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_psk_s* h = new (std::nothrow) uhsdr_psk_s();
+    if (!h) return UHSDR_DEVICE_ERROR;
+    h->a.C = num_channels;
+    h->a.text_capacity = text_capacity;
+    h->p = psk_params(speed_idx);
+    h->host = host;
+    h->stream = (hipStream_t)stream;
+    h->bytes = psk_layout(h, nullptr);
+    uhsdr_status st = h->alloc("psk");
+    if (st == UHSDR_OK)
+    {
+        psk_layout(h, (char*)h->mem);
+        st = h->upload_tables("psk", [h](char* image) { psk_fill_tables(h, image); });
+    }
+    if (st == UHSDR_OK) st = uhsdr_psk_reset(h);
+    if (st != UHSDR_OK) { uhsdr_psk_destroy(h); return st; }
+    *out = h;
     return UHSDR_OK;
 }
 
 extern "C" uhsdr_status uhsdr_psk_create(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, void* stream, uhsdr_psk_handle* out)
 {
-    const uhsdr_status st = psk_check(num_channels, speed_idx, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_psk_s* h = psk_new(num_channels, speed_idx, text_capacity, false);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->stream = (hipStream_t)stream;
-    const hipError_t e = hipMalloc(&h->mem, h->bytes);
-    if (e != hipSuccess)
-    {
-        uhsdr_set_error("psk: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-        delete h;
-        return UHSDR_DEVICE_ERROR;
-    }
-    psk_layout(h, (char*)h->mem);
-    uhsdr_status rs = UHSDR_DEVICE_ERROR;
-    char* tables = (char*)malloc(h->tables);
-    if (tables)
-    {
-        psk_fill_tables(h, tables);
-        const hipError_t ce = hipMemcpy(h->mem, tables, h->tables, hipMemcpyHostToDevice);
-        free(tables);
-        if (ce == hipSuccess) rs = uhsdr_psk_reset(h);
-        else uhsdr_set_error("psk: table upload failed: %s", hipGetErrorString(ce));
-    }
-    else uhsdr_set_error("psk: host allocation of %zu bytes failed", h->tables);
-    if (rs != UHSDR_OK) { (void)hipFree(h->mem); delete h; return rs; }
-    *out = h;
-    return UHSDR_OK;
+    return psk_create(num_channels, speed_idx, text_capacity, false, stream, out);
 }
 
 extern "C" uhsdr_status uhsdr_psk_create_host(int32_t num_channels, int32_t speed_idx, int32_t text_capacity, uhsdr_psk_handle* out)
 {
-    const uhsdr_status st = psk_check(num_channels, speed_idx, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_psk_s* h = psk_new(num_channels, speed_idx, text_capacity, true);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->mem = calloc(1, h->bytes);
-    if (!h->mem) { uhsdr_set_error("psk: host allocation of %zu bytes failed", h->bytes); delete h; return UHSDR_DEVICE_ERROR; }
-    psk_layout(h, (char*)h->mem);
-    psk_fill_tables(h, (char*)h->mem);
-    *out = h;
-    return UHSDR_OK;
+    return psk_create(num_channels, speed_idx, text_capacity, true, nullptr, out);
 }
 
 extern "C" uhsdr_status uhsdr_psk_destroy(uhsdr_psk_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (h->host) free(h->mem);
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-    }
+    h->release();
     delete h;
     return UHSDR_OK;
 }
 
-extern "C" uhsdr_status uhsdr_psk_set_stream(uhsdr_psk_handle h, void* stream)
-{
-    if (!h || h->host) { uhsdr_set_error("psk: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
-    h->stream = (hipStream_t)stream;
-    return UHSDR_OK;
-}
+extern "C" uhsdr_status uhsdr_psk_set_stream(uhsdr_psk_handle h, void* stream) { return arena_set_stream(h, "psk", stream, false); }
 
 static uhsdr_status psk_check_run(uhsdr_psk_handle h, const float* samples, int32_t n, int32_t stride)
 {
     if (!h || !samples) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (n < 0 || stride < 0 || n > stride) { uhsdr_set_error("psk: %d samples do not fit a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
-    return UHSDR_OK;
+    return arena_check_row("psk", "samples", n, n, stride);
 }
 
 static void psk_advance(uhsdr_psk_s* h, int32_t n)
@@ -271,7 +219,7 @@ extern "C" uhsdr_status uhsdr_psk_process(uhsdr_psk_handle h, const float* sampl
 {
     const uhsdr_status st = psk_check_run(h, samples, n, stride);
     if (st != UHSDR_OK) return st;
-    if (h->host) { uhsdr_set_error("psk: host handle, use uhsdr_psk_process_host"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, false, "psk", "uhsdr_psk_process_host")) return UHSDR_ARGUMENT_ERROR;
     if (n == 0) return UHSDR_OK;
     const int grid = (h->a.C + PSK_WG - 1) / PSK_WG;
     hipLaunchKernelGGL(psk_decode, dim3(grid), dim3(PSK_WG), 0, h->stream, h->a, h->p, h->k, samples, n, stride);
@@ -284,7 +232,7 @@ extern "C" uhsdr_status uhsdr_psk_process_host(uhsdr_psk_handle h, const float* 
 {
     const uhsdr_status st = psk_check_run(h, samples, n, stride);
     if (st != UHSDR_OK) return st;
-    if (!h->host) { uhsdr_set_error("psk: device handle, use uhsdr_psk_process"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, true, "psk", "uhsdr_psk_process")) return UHSDR_ARGUMENT_ERROR;
     for (int32_t c = 0; c < h->a.C; c++) psk_run_channel(h->a, c, h->p, h->k, samples + (size_t)c * stride, n);
     psk_advance(h, n);
     return UHSDR_OK;
@@ -301,7 +249,5 @@ extern "C" uhsdr_status uhsdr_psk_outputs(uhsdr_psk_handle h, uint8_t** text, ui
 
 extern "C" uhsdr_status uhsdr_psk_synchronize(uhsdr_psk_handle h)
 {
-    if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));
-    return UHSDR_OK;
+    return h ? h->synchronize() : UHSDR_ARGUMENT_ERROR;
 }

@@ -13,14 +13,10 @@
 // on 32 different banks (bank = (c * 33 + s) mod 32 = (c + s) mod 32).  The next tile's global
 // loads are issued before the current tile's arithmetic and land in the other LDS buffer after it.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 #include <new>
 
-#include "uhsdr_internal.h"
+#include "uhsdr_arena.h"
 #include "uhsdr_rtty.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 constexpr int RTTY_WG = 64;
 constexpr int RTTY_TILE = 32;
@@ -78,131 +74,90 @@ __global__ __launch_bounds__(RTTY_WG) void rtty_decode(RttyArena a, RttyParams p
     if (live) ch.store(a, c);
 }
 
-struct uhsdr_rtty_s
+struct uhsdr_rtty_s : ArenaMem
 {
     RttyArena a;
     RttyParams p;
-    void* mem;           // one allocation behind the arena
-    size_t bytes;
-    bool host;           // state in host memory (uhsdr_rtty_create_host)
-    hipStream_t stream;
 };
-
-static size_t rtty_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 static size_t rtty_layout(RttyArena& a, char* base)
 {
     const size_t C = (size_t)a.C;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += rtty_align(n); return p; };   // null base: size only
-    a.fs = (float*)take(sizeof(float) * RTTY_F_COUNT * C);
-    a.is = (int32_t*)take(sizeof(int32_t) * RTTY_I_COUNT * C);
-    a.total = (uint32_t*)take(sizeof(uint32_t) * C);
-    a.text = (uint8_t*)take(C * (size_t)a.text_capacity);
-    return off;
-}
-
-static uhsdr_status rtty_check(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx, int32_t text_capacity,
-                               const void* out)
-{
-    if (!out || num_channels < 1) { uhsdr_set_error("rtty: bad argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (shift_idx < 0 || shift_idx >= RTTY_SHIFT_COUNT) { uhsdr_set_error("rtty: shift_idx %d not 0 .. 5", shift_idx); return UHSDR_ARGUMENT_ERROR; }
-    if (speed_idx < 0 || speed_idx >= RTTY_SPEED_COUNT) { uhsdr_set_error("rtty: speed_idx %d not 0 .. 1", speed_idx); return UHSDR_ARGUMENT_ERROR; }
-    if (stopbits_idx < 0 || stopbits_idx >= RTTY_STOP_COUNT) { uhsdr_set_error("rtty: stopbits_idx %d not 0 .. 2", stopbits_idx); return UHSDR_ARGUMENT_ERROR; }
-    if (text_capacity < 8) { uhsdr_set_error("rtty: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
-    return UHSDR_OK;
-}
-
-static uhsdr_rtty_s* rtty_new(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx, int32_t atc_disable,
-                              int32_t text_capacity, bool host)
-{
-    uhsdr_rtty_s* h = new (std::nothrow) uhsdr_rtty_s();
-    if (!h) return nullptr;
-    h->a.C = num_channels;
-    h->a.text_capacity = text_capacity;
-    h->p = rtty_params(shift_idx, speed_idx, stopbits_idx, atc_disable);
-    h->host = host;
-    h->bytes = rtty_layout(h->a, nullptr);
-    return h;
+    ArenaCarver m{base, 0};
+    a.fs = m.take<float>(RTTY_F_COUNT * C);
+    a.is = m.take<int32_t>(RTTY_I_COUNT * C);
+    a.total = m.take<uint32_t>(C);
+    a.text = m.take<uint8_t>(C * (size_t)a.text_capacity);
+    return m.off;
 }
 
 // every static of the firmware's decoder starts at zero
 extern "C" uhsdr_status uhsdr_rtty_reset(uhsdr_rtty_handle h)
 {
     if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
-    if (h->host) memset(h->mem, 0, h->bytes);
-    else HIPCHK(hipMemsetAsync(h->mem, 0, h->bytes, h->stream));
+    return h->zero_state();
+}
+
+static uhsdr_status rtty_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx, int32_t atc_disable,
+                                int32_t text_capacity, bool host, void* stream, uhsdr_rtty_handle* out)
+{
+    if (!out || num_channels < 1) { uhsdr_set_error("rtty: bad argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (shift_idx < 0 || shift_idx >= RTTY_SHIFT_COUNT) { uhsdr_set_error("rtty: shift_idx %d not 0 .. 5", shift_idx); return UHSDR_ARGUMENT_ERROR; }
+    if (speed_idx < 0 || speed_idx >= RTTY_SPEED_COUNT) { uhsdr_set_error("rtty: speed_idx %d not 0 .. 1", speed_idx); return UHSDR_ARGUMENT_ERROR; }
+    if (stopbits_idx < 0 || stopbits_idx >= RTTY_STOP_COUNT) { uhsdr_set_error("rtty: stopbits_idx %d not 0 .. 2", stopbits_idx); return UHSDR_ARGUMENT_ERROR; }
+    if (text_capacity < 8) { uhsdr_set_error("rtty: text_capacity %d below 8", text_capacity); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_rtty_s* h = new (std::nothrow) uhsdr_rtty_s();
+    if (!h) return UHSDR_DEVICE_ERROR;
+    h->a.C = num_channels;
+    h->a.text_capacity = text_capacity;
+    h->p = rtty_params(shift_idx, speed_idx, stopbits_idx, atc_disable);
+    h->host = host;
+    h->stream = (hipStream_t)stream;
+    h->bytes = rtty_layout(h->a, nullptr);
+    uhsdr_status st = h->alloc("rtty");
+    if (st == UHSDR_OK)
+    {
+        rtty_layout(h->a, (char*)h->mem);
+        st = h->zero_state();
+    }
+    if (st != UHSDR_OK) { uhsdr_rtty_destroy(h); return st; }
+    *out = h;
     return UHSDR_OK;
 }
 
 extern "C" uhsdr_status uhsdr_rtty_create(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
                                           int32_t atc_disable, int32_t text_capacity, void* stream, uhsdr_rtty_handle* out)
 {
-    const uhsdr_status st = rtty_check(num_channels, shift_idx, speed_idx, stopbits_idx, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_rtty_s* h = rtty_new(num_channels, shift_idx, speed_idx, stopbits_idx, atc_disable, text_capacity, false);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->stream = (hipStream_t)stream;
-    const hipError_t e = hipMalloc(&h->mem, h->bytes);
-    if (e != hipSuccess)
-    {
-        uhsdr_set_error("rtty: device allocation of %zu bytes failed: %s", h->bytes, hipGetErrorString(e));
-        delete h;
-        return UHSDR_DEVICE_ERROR;
-    }
-    rtty_layout(h->a, (char*)h->mem);
-    const uhsdr_status rs = uhsdr_rtty_reset(h);
-    if (rs != UHSDR_OK) { (void)hipFree(h->mem); delete h; return rs; }
-    *out = h;
-    return UHSDR_OK;
+    return rtty_create(num_channels, shift_idx, speed_idx, stopbits_idx, atc_disable, text_capacity, false, stream, out);
 }
 
 extern "C" uhsdr_status uhsdr_rtty_create_host(int32_t num_channels, int32_t shift_idx, int32_t speed_idx, int32_t stopbits_idx,
                                                int32_t atc_disable, int32_t text_capacity, uhsdr_rtty_handle* out)
 {
-    const uhsdr_status st = rtty_check(num_channels, shift_idx, speed_idx, stopbits_idx, text_capacity, out);
-    if (st != UHSDR_OK) return st;
-    uhsdr_rtty_s* h = rtty_new(num_channels, shift_idx, speed_idx, stopbits_idx, atc_disable, text_capacity, true);
-    if (!h) return UHSDR_DEVICE_ERROR;
-    h->mem = calloc(1, h->bytes);
-    if (!h->mem) { uhsdr_set_error("rtty: host allocation of %zu bytes failed", h->bytes); delete h; return UHSDR_DEVICE_ERROR; }
-    rtty_layout(h->a, (char*)h->mem);
-    *out = h;
-    return UHSDR_OK;
+    return rtty_create(num_channels, shift_idx, speed_idx, stopbits_idx, atc_disable, text_capacity, true, nullptr, out);
 }
 
 extern "C" uhsdr_status uhsdr_rtty_destroy(uhsdr_rtty_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (h->host) free(h->mem);
-    else
-    {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(h->mem);
-    }
+    h->release();
     delete h;
     return UHSDR_OK;
 }
 
-extern "C" uhsdr_status uhsdr_rtty_set_stream(uhsdr_rtty_handle h, void* stream)
-{
-    if (!h || h->host) { uhsdr_set_error("rtty: not a device handle"); return UHSDR_ARGUMENT_ERROR; }
-    h->stream = (hipStream_t)stream;
-    return UHSDR_OK;
-}
+extern "C" uhsdr_status uhsdr_rtty_set_stream(uhsdr_rtty_handle h, void* stream) { return arena_set_stream(h, "rtty", stream, false); }
 
 static uhsdr_status rtty_check_run(uhsdr_rtty_handle h, const float* samples, int32_t n, int32_t stride)
 {
     if (!h || !samples) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
-    if (n < 0 || stride < 0 || n > stride) { uhsdr_set_error("rtty: %d samples do not fit a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
-    return UHSDR_OK;
+    return arena_check_row("rtty", "samples", n, n, stride);
 }
 
 extern "C" uhsdr_status uhsdr_rtty_process(uhsdr_rtty_handle h, const float* samples, int32_t n, int32_t stride)
 {
     const uhsdr_status st = rtty_check_run(h, samples, n, stride);
     if (st != UHSDR_OK) return st;
-    if (h->host) { uhsdr_set_error("rtty: host handle, use uhsdr_rtty_process_host"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, false, "rtty", "uhsdr_rtty_process_host")) return UHSDR_ARGUMENT_ERROR;
     if (n == 0) return UHSDR_OK;
     const int grid = (h->a.C + RTTY_WG - 1) / RTTY_WG;
     hipLaunchKernelGGL(rtty_decode, dim3(grid), dim3(RTTY_WG), 0, h->stream, h->a, h->p, samples, n, stride);
@@ -214,7 +169,7 @@ extern "C" uhsdr_status uhsdr_rtty_process_host(uhsdr_rtty_handle h, const float
 {
     const uhsdr_status st = rtty_check_run(h, samples, n, stride);
     if (st != UHSDR_OK) return st;
-    if (!h->host) { uhsdr_set_error("rtty: device handle, use uhsdr_rtty_process"); return UHSDR_ARGUMENT_ERROR; }
+    if (arena_wrong_kind(h, true, "rtty", "uhsdr_rtty_process")) return UHSDR_ARGUMENT_ERROR;
     for (int32_t c = 0; c < h->a.C; c++) rtty_run_channel(h->a, c, h->p, samples + (size_t)c * stride, n);
     return UHSDR_OK;
 }
@@ -229,7 +184,5 @@ extern "C" uhsdr_status uhsdr_rtty_outputs(uhsdr_rtty_handle h, uint8_t** text, 
 
 extern "C" uhsdr_status uhsdr_rtty_synchronize(uhsdr_rtty_handle h)
 {
-    if (!h) return UHSDR_ARGUMENT_ERROR;
-    if (!h->host) HIPCHK(hipStreamSynchronize(h->stream));
-    return UHSDR_OK;
+    return h ? h->synchronize() : UHSDR_ARGUMENT_ERROR;
 }

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi
+from ._handle import TextSender
 
 IAM_B, IAM_A, STRAIGHT, ULTIMATE = range(4)
 DIT, DAH = 1, 2                                     # bits of a key byte
@@ -22,47 +22,19 @@ class _Config(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("keyer_mode", "keyer_speed", "keyer_weight", "paddle_reverse", "rx_delay", "sidetone_freq")]
 
 
-class CwGenerator:
+class CwGenerator(TextSender):
+    kind = "cwgen"
+
     def __init__(self, channels: int, mode: int = IAM_B, speed: int = 20, weight: int = 100, reverse: bool = False, rx_delay: int = 8,
                  sidetone: int = 750, capacity: int = 128, echo_capacity: int = 256, host: bool = False, stream: int | None = None):
-        self.lib = _abi.load()
-        self.channels, self.host = int(channels), bool(host)
         self.text_capacity, self.echo_capacity = int(capacity), int(echo_capacity)
         cfg = _Config(int(mode), int(speed), int(weight), int(bool(reverse)), int(rx_delay), int(sidetone))
-        h = C.c_void_p()
-        if host:
-            self._call("create_host", self.channels, C.byref(cfg), self.text_capacity, self.echo_capacity, C.byref(h), handle=False)
-        else:
-            self._call("create", self.channels, C.byref(cfg), self.text_capacity, self.echo_capacity, C.c_void_p(stream or 0), C.byref(h), handle=False)
-        self.handle = h
+        self._create(channels, (C.byref(cfg), self.text_capacity, self.echo_capacity), host, stream)
         self._blocks = 0
-
-    def _call(self, name: str, *args, handle: bool = True):
-        fn = f"uhsdr_cwgen_{name}"
-        _abi.check(getattr(self.lib, fn)(*((self.handle,) if handle else ()), *args), fn)
-
-    def reset(self) -> None:
-        self._call("reset")
 
     def set_speed(self, speed: int, weight: int = 100) -> None:
         """CwGen_SetSpeed; holds from the next process call on"""
         self._call("set_speed", int(speed), int(weight))
-
-    def put_text(self, text) -> np.ndarray:
-        """text: one bytes object per channel (or one for all).  Appends what fits to every channel's
-        queue and returns the accepted counts, int32 [C].  Waits for the work enqueued."""
-        if isinstance(text, (bytes, bytearray)):
-            text = [bytes(text)] * self.channels
-        if len(text) != self.channels:
-            raise ValueError("one text per channel")
-        length = np.array([len(t) for t in text], np.int32)
-        stride = max(1, int(length.max()))
-        rows = np.zeros((self.channels, stride), np.uint8)
-        for c, t in enumerate(text):
-            rows[c, :len(t)] = np.frombuffer(bytes(t), np.uint8)
-        accepted = np.zeros(self.channels, np.int32)
-        self._call("put_text", rows.ctypes.data_as(C.c_void_p), length.ctypes.data_as(C.c_void_p), stride, accepted.ctypes.data_as(C.c_void_p))
-        return accepted
 
     def process(self, keys, i, q, n: int | None = None) -> None:
         """keys: uint8 [C][n/32]; i, q: float32 [C][stride].  Contiguous numpy arrays for a host
@@ -74,15 +46,10 @@ class CwGenerator:
         n = stride if n is None else int(n)
         if tuple(keys.shape) != (self.channels, n // BLOCK):
             raise ValueError("keys must be [C][n/32]")
-        if self.host:
-            if i.dtype != np.float32 or q.dtype != np.float32 or keys.dtype != np.uint8 or not (i.flags.c_contiguous and q.flags.c_contiguous and keys.flags.c_contiguous):
-                raise ValueError("keys must be a contiguous uint8 array, i and q contiguous float32 arrays")
-            self._call("process_host", keys.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), n, stride)
-        else:
-            import torch
-            if i.dtype != torch.float32 or q.dtype != torch.float32 or keys.dtype != torch.uint8 or not (i.is_contiguous() and q.is_contiguous() and keys.is_contiguous()):
-                raise ValueError("keys must be a contiguous uint8 tensor, i and q contiguous float32 tensors")
-            self._call("process", C.c_void_p(keys.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(q.data_ptr()), n, stride)
+        if not (self._fits(keys, np.uint8) and self._fits(i, np.float32) and self._fits(q, np.float32)):
+            raise ValueError("keys must be a contiguous uint8 array, i and q contiguous float32 arrays" if self.host else
+                             "keys must be a contiguous uint8 tensor, i and q contiguous float32 tensors")
+        self._call("process_host" if self.host else "process", self._ptr(keys), self._ptr(i), self._ptr(q), n, stride)
         self._blocks = n // BLOCK
 
     def generate(self, keys: np.ndarray):
@@ -100,27 +67,9 @@ class CwGenerator:
         self.synchronize()
         return i.cpu().numpy(), q.cpu().numpy()
 
-    def set_stream(self, stream: int) -> None:
-        self._call("set_stream", C.c_void_p(stream))
-
-    def synchronize(self) -> None:
-        self._call("synchronize")
-
-    def _fetch(self, ptr, shape, dtype) -> np.ndarray:
-        arr = np.empty(shape, dtype)
-        if arr.nbytes == 0:
-            return arr
-        if self.host:
-            C.memmove(arr.ctypes.data, ptr, arr.nbytes)
-        else:
-            _abi.check(self.lib.uhsdr_copy_to_host(arr.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), arr.nbytes), "uhsdr_copy_to_host")
-        return arr
-
     def _outputs(self):
         self.synchronize()
-        p = [C.c_void_p() for _ in range(5)]
-        self._call("outputs", *(C.byref(x) for x in p))
-        return [x.value for x in p]
+        return self._pointers("outputs", 5)
 
     def flags(self) -> np.ndarray:
         """uint8 [C][blocks] of the last process call"""
@@ -153,14 +102,3 @@ class CwGenerator:
         self._call("peek", C.byref(p), C.byref(rows))
         words = self._fetch(p.value, (rows.value, self.channels), np.uint32)
         return dict(zip(WORDS, words))
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.uhsdr_cwgen_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
