@@ -20,10 +20,10 @@ ORACLE  := oracle/build/libuhsdr_oracle.so
 OBJDIR  := uhsdr_amd/build
 
 HOST_SRCS := uhsdr_amd/csrc/uhsdr_setup.c uhsdr_amd/csrc/uhsdr_filter_tables.c
-HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip uhsdr_amd/csrc/uhsdr_nr.hip
+HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip uhsdr_amd/csrc/uhsdr_nr.hip uhsdr_amd/csrc/uhsdr_nb.hip
 HOST_OBJS := $(patsubst uhsdr_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRCS))
 HIP_OBJS  := $(patsubst uhsdr_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
-HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_arena.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h uhsdr_amd/csrc/uhsdr_nr.h uhsdr_amd/csrc/uhsdr_nr_tables.h uhsdr_amd/csrc/uhsdr_libm_expf.h
+HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_arena.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h uhsdr_amd/csrc/uhsdr_nr.h uhsdr_amd/csrc/uhsdr_nr_tables.h uhsdr_amd/csrc/uhsdr_libm_expf.h uhsdr_amd/csrc/uhsdr_nb.h
 
 EXAMPLE := examples/build/rx_batch
 

@@ -1023,15 +1023,28 @@ uhsdr_status uhsdr_cwgen_destroy(uhsdr_cwgen_handle h);
  * + M - 2 <= 127 (width 4: VAD_high >= 17, VAD_low <= 116), or the band is empty.  A frame whose
  * band holds no power has a NaN power_ratio, which the C converts to int (undefined); here that
  * frame has NN = 1.
- * Not built: the noise blanker (alt_noise_blanking), the LMS noise reduction, the #if 0 notch code,
- * the noise reduction inside the RX chain. */
+ * The noise blanker in front (uhsdr_nb_* below has the blanker itself): AudioNr_RunNoiseReduction runs
+ * alt_noise_blanking on every collected frame, in place, before spectral_noise_reduction_3, and the
+ * firmware offers NR alone, NB alone and NB followed by NR.
+ *   nb_setting            0 (default): no blanker; 1 .. 15: ts.dsp.nb_setting, the blanker runs on
+ *                         every frame before the noise reduction, as a launch of its own
+ *   nr_bypass             0 (default); 1: the firmware's NB-only setting, the frame is copied
+ *                         through behind the blanker and no noise reduction state moves.  With
+ *                         nb_setting 0 it is refused (UHSDR_ARGUMENT_ERROR): the firmware does not
+ *                         enter the stream at all then
+ * process, process_host, process_frames and process_frames_host honour both; reset clears the
+ * blanker too; with both 0 every call enqueues exactly what it enqueued before they existed.  With
+ * the blanker on, a frame's output lags by 13 samples more.
+ * Not built: the LMS noise reduction, the #if 0 notch code, the noise reduction or the blanker
+ * inside the RX chain. */
 typedef struct uhsdr_nr_config
 {
     float   alpha;
     int32_t asnr, width, power_threshold_int;
     int32_t width_hz, offset_hz;
     int32_t sample_rate;
-    int32_t reserved[9];
+    int32_t nb_setting, nr_bypass;
+    int32_t reserved[7];
 } uhsdr_nr_config;
 typedef struct uhsdr_nr_s* uhsdr_nr_handle;
 
@@ -1105,6 +1118,49 @@ int32_t      uhsdr_rx_kernel_count(uhsdr_rx_handle h);
 uhsdr_status uhsdr_rx_enable_timing(uhsdr_rx_handle h, int32_t enable);
 int32_t      uhsdr_rx_kernel_times(uhsdr_rx_handle h, float* total_ms, int32_t* launches, int32_t max_kernels);
 const char*  uhsdr_rx_kernel_name(int32_t index);
+
+/* ---- Noise blanker: 12 / 6 ksps audio in, the same audio with impulses repaired ----
+ * The firmware's alt_noise_blanking (drivers/audio/audio_nr.c:2210-2535), one instance per channel,
+ * on the 128-sample frames of the noise reduction: an order-10 LPC analysis of the frame
+ * (autocorrelation, Levinson-Durbin), the inverse filter and its matched filter, a threshold of
+ * (16 - nb_setting) * 0.5 * sqrt(variance * power of the coefficients) on the result, and up to five
+ * places per frame where seven samples are replaced by the weighted forward and backward
+ * predictions.  Exact to the reference: the same binary32 output at every sample.
+ *   nb_setting   ts.dsp.nb_setting, 1 .. 15 (MAX_NB_SETTING), default 8; a higher setting lowers
+ *                the threshold.  The firmware's 0 means off; anything outside 1 .. 15 is
+ *                UHSDR_ARGUMENT_ERROR
+ * process_frames: in, out = f32 [C][stride], `frames` frames of 128 samples each per row, frames *
+ * 128 <= stride, device memory (host memory for process_frames_host), stream-ordered.  in == out is
+ * allowed, the firmware works in place; any other overlap is the caller's error.  The blanker keeps
+ * the last 26 samples, so a frame's output lags the input by 13 samples.
+ * state: per channel, into host arrays of num_channels (null: not wanted), after everything
+ * enqueued: the places repaired in the last frame (0 .. 5) and since the last reset.  The
+ * firmware keeps the count in a local; this is the activity a host would show.
+ * Reference oddities kept: nothing is clamped; a silent frame, or one whose autocorrelation
+ * overflows, has a NaN threshold, nothing compares above it and the samples pass; the search skips
+ * the filtered samples 0 .. 12 and a repair lies 10 samples before its hit.  create and reset start
+ * from a cleared working buffer, while the firmware never clears its static, not even when the noise
+ * reduction restarts (as with the NR's overlap half above).
+ * Not built: the old time-domain blanker of audio_driver.c:1278, the blanker inside the RX chain or
+ * uhsdr_i2s_*. */
+typedef struct uhsdr_nb_config
+{
+    int32_t nb_setting;
+    int32_t reserved[7];
+} uhsdr_nb_config;
+typedef struct uhsdr_nb_s* uhsdr_nb_handle;
+
+void         uhsdr_nb_config_default(uhsdr_nb_config* cfg);
+uhsdr_status uhsdr_nb_create(int32_t num_channels, const uhsdr_nb_config* cfg, void* stream, uhsdr_nb_handle* out);
+/* the same blanker with its state in host memory, for the _host call (no device call) */
+uhsdr_status uhsdr_nb_create_host(int32_t num_channels, const uhsdr_nb_config* cfg, uhsdr_nb_handle* out);
+uhsdr_status uhsdr_nb_reset(uhsdr_nb_handle h);
+uhsdr_status uhsdr_nb_set_stream(uhsdr_nb_handle h, void* stream);
+uhsdr_status uhsdr_nb_process_frames(uhsdr_nb_handle h, const float* in, float* out, int32_t frames, int32_t stride);
+uhsdr_status uhsdr_nb_process_frames_host(uhsdr_nb_handle h, const float* in, float* out, int32_t frames, int32_t stride);
+uhsdr_status uhsdr_nb_state(uhsdr_nb_handle h, int32_t* last_count, uint32_t* total_count);
+uhsdr_status uhsdr_nb_synchronize(uhsdr_nb_handle h);
+uhsdr_status uhsdr_nb_destroy(uhsdr_nb_handle h);
 
 #ifdef __cplusplus
 }

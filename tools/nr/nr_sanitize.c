@@ -7,9 +7,10 @@
  *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
  *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
  *         -c -x hip uhsdr_amd/csrc/uhsdr_nr.hip -o /tmp/nr.o
+ *   (the same line for uhsdr_amd/csrc/uhsdr_nb.hip -> /tmp/nb.o: the stream can hold a noise blanker)
  *   for f in uhsdr_amd/csrc/uhsdr_setup tools/nr/nr_sanitize uhsdr_amd/csrc/uhsdr_filter_tables; do
  *       gcc -O1 -g $S -ffp-contract=off -Iinclude -c $f.c -o /tmp/$(basename $f).o; done
- *   hipcc -fsanitize=address,undefined /tmp/nr.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o /tmp/nr_sanitize.o \
+ *   hipcc -fsanitize=address,undefined /tmp/nr.o /tmp/nb.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o /tmp/nr_sanitize.o \
  *         -lm -o /tmp/nr_sanitize
  *   /tmp/nr_sanitize /tmp/nr_cases.bin
  *

@@ -27,3 +27,4 @@ from .psk import PskDecoder  # noqa: F401
 from .digimod import RttyModulator, PskModulator  # noqa: F401
 from .cwgen import CwGenerator  # noqa: F401
 from .nr import NrProcessor, nr_config, nr_band  # noqa: F401
+from .nb import NbProcessor, nb_config  # noqa: F401

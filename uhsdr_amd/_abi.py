@@ -169,8 +169,13 @@ class SpectrumPlan(C.Structure):
 class NrConfig(C.Structure):
     _fields_ = [
         ("alpha", C.c_float), ("asnr", C.c_int32), ("width", C.c_int32), ("power_threshold_int", C.c_int32),
-        ("width_hz", C.c_int32), ("offset_hz", C.c_int32), ("sample_rate", C.c_int32), ("reserved", C.c_int32 * 9),
+        ("width_hz", C.c_int32), ("offset_hz", C.c_int32), ("sample_rate", C.c_int32), ("nb_setting", C.c_int32),
+        ("nr_bypass", C.c_int32), ("reserved", C.c_int32 * 7),
     ]
+
+
+class NbConfig(C.Structure):
+    _fields_ = [("nb_setting", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 # every exported entry point of include/uhsdr.h: name -> (restype, argtypes)
@@ -331,6 +336,16 @@ SIGNATURES = {
     "uhsdr_nr_synchronize": (C.c_int, [C.c_void_p]),
     "uhsdr_nr_destroy": (C.c_int, [C.c_void_p]),
     "uhsdr_nr_cfft256_host": (C.c_int, [C.c_void_p, C.c_int32]),
+    "uhsdr_nb_config_default": (None, [C.POINTER(NbConfig)]),
+    "uhsdr_nb_create": (C.c_int, [C.c_int32, C.POINTER(NbConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_nb_create_host": (C.c_int, [C.c_int32, C.POINTER(NbConfig), C.POINTER(C.c_void_p)]),
+    "uhsdr_nb_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_nb_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_nb_process_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nb_process_frames_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "uhsdr_nb_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhsdr_nb_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_nb_destroy": (C.c_int, [C.c_void_p]),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

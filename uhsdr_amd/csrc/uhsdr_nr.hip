@@ -358,6 +358,7 @@ struct uhsdr_nr_s : ArenaMem               // one allocation: window, plan, coef
     int cur;                            // which queue row is current
     float* work;                        // W, Y, Z rows of one call
     size_t work_row;                    // floats per row of each
+    uhsdr_nb_handle nb;                 // the noise blanker in front (cfg.nb_setting > 0), of the handle's kind and on its stream
 };
 
 static size_t nr_layout(uhsdr_nr_s* h, char* base)
@@ -452,6 +453,11 @@ extern "C" uhsdr_status uhsdr_nr_reset(uhsdr_nr_handle h)
     const size_t floats = h->floats_end - h->tables;      // every float of the state, the stream's included
     h->seen = 0;
     h->cur = 0;
+    if (h->nb)
+    {
+        const uhsdr_status st = uhsdr_nb_reset(h->nb);
+        if (st != UHSDR_OK) return st;
+    }
     if (h->host)
     {
         memset(h->a.fs, 0, floats);
@@ -475,6 +481,10 @@ static uhsdr_status nr_create(int32_t num_channels, const uhsdr_nr_config* cfg, 
     NrParams p;
     uhsdr_status st = nr_params(cfg, &p);
     if (st != UHSDR_OK) return st;
+    if (cfg->nb_setting < 0 || cfg->nb_setting > 15) { uhsdr_set_error("nr: nb_setting %d outside 0..15", cfg->nb_setting); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->nr_bypass != 0 && cfg->nr_bypass != 1) { uhsdr_set_error("nr: nr_bypass %d: 0 or 1", cfg->nr_bypass); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->nr_bypass && !cfg->nb_setting)
+    { uhsdr_set_error("nr: nr_bypass without the noise blanker (nb_setting 0): the firmware does not enter the stream then"); return UHSDR_ARGUMENT_ERROR; }
     uhsdr_nr_s* h = new (std::nothrow) uhsdr_nr_s();
     if (!h) { uhsdr_set_error("nr: host allocation of the handle failed"); return UHSDR_DEVICE_ERROR; }
     h->a.C = num_channels;
@@ -512,6 +522,13 @@ static uhsdr_status nr_create(int32_t num_channels, const uhsdr_nr_config* cfg, 
         }
         if (e != hipSuccess) { uhsdr_set_error("nr: table upload failed: %s", hipGetErrorString(e)); st = UHSDR_DEVICE_ERROR; }
     }
+    if (st == UHSDR_OK && cfg->nb_setting)
+    {
+        uhsdr_nb_config nc;
+        uhsdr_nb_config_default(&nc);
+        nc.nb_setting = cfg->nb_setting;
+        st = host ? uhsdr_nb_create_host(num_channels, &nc, &h->nb) : uhsdr_nb_create(num_channels, &nc, stream, &h->nb);
+    }
     if (st == UHSDR_OK) st = uhsdr_nr_reset(h);
     if (st != UHSDR_OK) { uhsdr_nr_destroy(h); return st; }
     *out = h;
@@ -532,6 +549,7 @@ extern "C" uhsdr_status uhsdr_nr_destroy(uhsdr_nr_handle h)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
     h->release();
+    if (h->nb) uhsdr_nb_destroy(h->nb);
     if (h->host) free(h->work);
     else if (h->work) (void)hipFree(h->work);
     free(h->host_plan);
@@ -539,7 +557,44 @@ extern "C" uhsdr_status uhsdr_nr_destroy(uhsdr_nr_handle h)
     return UHSDR_OK;
 }
 
-extern "C" uhsdr_status uhsdr_nr_set_stream(uhsdr_nr_handle h, void* stream) { return arena_set_stream(h, "nr", stream, false); }
+extern "C" uhsdr_status uhsdr_nr_set_stream(uhsdr_nr_handle h, void* stream)
+{
+    const uhsdr_status st = arena_set_stream(h, "nr", stream, false);
+    return st == UHSDR_OK && h->nb ? uhsdr_nb_set_stream(h->nb, stream) : st;
+}
+
+// The call's work rows W, Y, Z of `row` floats each per channel; they only grow
+static uhsdr_status nr_work_rows(uhsdr_nr_handle h, size_t row)
+{
+    if (row <= h->work_row) return UHSDR_OK;
+    const size_t bytes = sizeof(float) * 3 * row * (size_t)h->a.C;
+    if (h->host)
+    {
+        free(h->work);
+        h->work = (float*)malloc(bytes);
+    }
+    else
+    {
+        HIPCHK(hipStreamSynchronize(h->stream));       // earlier calls still read the rows
+        if (h->work) (void)hipFree(h->work);
+        h->work = nullptr;
+        if (hipMalloc((void**)&h->work, bytes) != hipSuccess) h->work = nullptr;
+    }
+    if (!h->work) { h->work_row = 0; uhsdr_set_error("nr: allocation of %zu bytes failed", bytes); return UHSDR_DEVICE_ERROR; }
+    h->work_row = row;
+    return UHSDR_OK;
+}
+
+// frames W -> Y without the noise reduction (nr_bypass): the copy AudioNr_RunNoiseReduction ends with
+static uhsdr_status nr_copy_frames(uhsdr_nr_handle h, const float* src, size_t src_row, float* dst, size_t dst_row, int frames)
+{
+    const size_t width = sizeof(float) * NR_BINS * (size_t)frames;
+    if (h->host)
+        for (int32_t c = 0; c < h->a.C; c++) memcpy(dst + (size_t)c * dst_row, src + (size_t)c * src_row, width);
+    else
+        HIPCHK(hipMemcpy2DAsync(dst, sizeof(float) * dst_row, src, sizeof(float) * src_row, width, (size_t)h->a.C, hipMemcpyDeviceToDevice, h->stream));
+    return UHSDR_OK;
+}
 
 static uhsdr_status nr_check_run(uhsdr_nr_handle h, const float* in, float* out, int32_t frames, int32_t stride)
 {
@@ -555,6 +610,16 @@ extern "C" uhsdr_status uhsdr_nr_process_frames(uhsdr_nr_handle h, const float* 
     if (st != UHSDR_OK) return st;
     if (arena_wrong_kind(h, false, "nr", "uhsdr_nr_process_frames_host")) return UHSDR_ARGUMENT_ERROR;
     if (frames == 0) return UHSDR_OK;
+    if (h->nb)
+    {
+        // the blanker's result goes to the output rows (nr_bypass), or to work rows of the caller's
+        // stride, which the noise reduction reads
+        if (h->cfg.nr_bypass) return uhsdr_nb_process_frames(h->nb, in, out, frames, stride);
+        uhsdr_status sn = nr_work_rows(h, (size_t)stride);
+        if (sn == UHSDR_OK) sn = uhsdr_nb_process_frames(h->nb, in, h->work, frames, stride);
+        if (sn != UHSDR_OK) return sn;
+        in = h->work;
+    }
     const int grid = (h->a.C + NR_WAVES - 1) / NR_WAVES;
     hipLaunchKernelGGL(nr_frames, dim3(grid), dim3(NR_WAVES * 64), 0, h->stream, h->a, h->p, in, out, frames, stride);
     HIPCHK(hipGetLastError());
@@ -566,6 +631,14 @@ extern "C" uhsdr_status uhsdr_nr_process_frames_host(uhsdr_nr_handle h, const fl
     const uhsdr_status st = nr_check_run(h, in, out, frames, stride);
     if (st != UHSDR_OK) return st;
     if (arena_wrong_kind(h, true, "nr", "uhsdr_nr_process_frames")) return UHSDR_ARGUMENT_ERROR;
+    if (h->nb && frames)
+    {
+        if (h->cfg.nr_bypass) return uhsdr_nb_process_frames_host(h->nb, in, out, frames, stride);
+        uhsdr_status sn = nr_work_rows(h, (size_t)stride);
+        if (sn == UHSDR_OK) sn = uhsdr_nb_process_frames_host(h->nb, in, h->work, frames, stride);
+        if (sn != UHSDR_OK) return sn;
+        in = h->work;
+    }
     for (int32_t c = 0; c < h->a.C; c++)
         for (int32_t f = 0; f < frames; f++)
             nr_frame_host(h->a.plan, h->a.window, &h->p, h->a.fs + (size_t)c * NR_STATE_FLOATS, h->a.is + (size_t)c * NR_I_COUNT,
@@ -653,7 +726,7 @@ static uhsdr_status nr_stream_call(uhsdr_nr_handle h, const float* in, float* ou
     if (n < 0 || stride < 0 || n > stride || n % 8 != 0)
     { uhsdr_set_error("nr: %d samples: a multiple of 8 that fits a row of %d", n, stride); return UHSDR_LENGTH_ERROR; }
     if (arena_wrong_kind(h, host, "nr", host ? "uhsdr_nr_process" : "uhsdr_nr_process_host")) return UHSDR_ARGUMENT_ERROR;
-    if (h->stream_status != UHSDR_OK)
+    if (h->stream_status != UHSDR_OK && !h->cfg.nr_bypass)
     { uhsdr_set_error("nr: the band at the stream's frame rate (%d) is refused", h->decimated ? 6000 : 12000); return h->stream_status; }
     k->decimated = h->decimated;
     k->n = n;
@@ -668,25 +741,8 @@ static uhsdr_status nr_stream_call(uhsdr_nr_handle h, const float* in, float* ou
     k->E1 = T1 > NR_LATENCY ? T1 - NR_LATENCY : 0;
     k->stride = stride;
     // the work rows W, Y, Z: fill + m <= 127 + m floats each
-    const size_t row = (size_t)NR_BINS + (size_t)k->m;
-    if (row > h->work_row)
-    {
-        const size_t bytes = sizeof(float) * 3 * row * (size_t)h->a.C;
-        if (h->host)
-        {
-            free(h->work);
-            h->work = (float*)malloc(bytes);
-        }
-        else
-        {
-            HIPCHK(hipStreamSynchronize(h->stream));       // earlier calls still read the rows
-            if (h->work) (void)hipFree(h->work);
-            h->work = nullptr;
-            if (hipMalloc((void**)&h->work, bytes) != hipSuccess) h->work = nullptr;
-        }
-        if (!h->work) { h->work_row = 0; uhsdr_set_error("nr: allocation of %zu bytes failed", bytes); return UHSDR_DEVICE_ERROR; }
-        h->work_row = row;
-    }
+    const uhsdr_status sw = nr_work_rows(h, (size_t)NR_BINS + (size_t)k->m);
+    if (sw != UHSDR_OK) return sw;
     k->work_row = (int)h->work_row;
     return UHSDR_OK;
 }
@@ -706,7 +762,14 @@ extern "C" uhsdr_status uhsdr_nr_process(uhsdr_nr_handle h, const float* in, flo
     float *W = h->work, *Y = h->work + plane, *Z = h->work + 2 * plane;
     auto blocks = [](size_t elems) { return dim3((unsigned)((elems + 255) / 256)); };
     hipLaunchKernelGGL(nr_stream_pre, blocks(C * (k.fill + k.m)), dim3(256), 0, h->stream, h->a, k, in, W);
-    if (k.frames)
+    if (k.frames && h->nb)
+    {
+        // the blanker works on the collected frames in place, as the firmware does, in a launch of its own
+        uhsdr_status sn = uhsdr_nb_process_frames(h->nb, W, W, k.frames, k.work_row);
+        if (sn == UHSDR_OK && h->cfg.nr_bypass) sn = nr_copy_frames(h, W, h->work_row, Y, h->work_row, k.frames);
+        if (sn != UHSDR_OK) return sn;
+    }
+    if (k.frames && !h->cfg.nr_bypass)
         hipLaunchKernelGGL(nr_frames, dim3((h->a.C + NR_WAVES - 1) / NR_WAVES), dim3(NR_WAVES * 64), 0, h->stream, h->a, h->sp, (const float*)W, Y,
                            k.frames, k.work_row);
     hipLaunchKernelGGL(nr_stream_fifo, blocks(C * k.m), dim3(256), 0, h->stream, h->a, k, (const float*)h->a.queue[h->cur], (const float*)Y, Z);
@@ -729,10 +792,20 @@ extern "C" uhsdr_status uhsdr_nr_process_host(uhsdr_nr_handle h, const float* in
     const float* queue = a.queue[h->cur];
     for (int32_t c = 0; c < a.C; c++)
     {
-        float *w = W + (size_t)c * k.work_row, *y = Y + (size_t)c * k.work_row, *z = Z + (size_t)c * k.work_row;
+        float* w = W + (size_t)c * k.work_row;
         for (int i = 0; i < k.fill + k.m; i++)
             w[i] = nr_stream_work(in + (size_t)c * stride, a.pend + (size_t)c * NR_BINS, a.dec_hist + (size_t)c * 4, a.dec_coeffs, k.decimated, k.fill, i);
-        for (int f = 0; f < k.frames; f++)
+    }
+    if (k.frames && h->nb)
+    {
+        uhsdr_status sn = uhsdr_nb_process_frames_host(h->nb, W, W, k.frames, k.work_row);
+        if (sn == UHSDR_OK && h->cfg.nr_bypass) sn = nr_copy_frames(h, W, h->work_row, Y, h->work_row, k.frames);
+        if (sn != UHSDR_OK) return sn;
+    }
+    for (int32_t c = 0; c < a.C; c++)
+    {
+        float *w = W + (size_t)c * k.work_row, *y = Y + (size_t)c * k.work_row, *z = Z + (size_t)c * k.work_row;
+        for (int f = 0; f < (h->cfg.nr_bypass ? 0 : k.frames); f++)
             nr_frame_host(a.plan, a.window, &h->sp, a.fs + (size_t)c * NR_STATE_FLOATS, a.is + (size_t)c * NR_I_COUNT, w + f * NR_BINS, y + f * NR_BINS);
         for (int i = 0; i < k.m; i++) z[i] = nr_stream_emit(queue + (size_t)c * NR_QUEUE, y, k.T0, k.E0, k.P0, i);
         for (int o = 0; o < k.n; o++)

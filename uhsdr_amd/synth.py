@@ -734,3 +734,59 @@ def nr_fixture(path: str) -> dict:
     g["audio"] = audio
     g["cfg"] = json.loads(str(g["config"]))
     return g
+
+
+def nb_audio(nsamples: int, seed: int = 0, kind: str = "voiced", sigma: float = 300.0, a1: float = 1.6, a2: float = -0.8,
+             impulses=(), scale: float = 1.0, tone: float = 1000.0, rate: float = 12000.0, amplitude: float = 3000.0,
+             nan_at: int = -1, inf_at: int = -1, ramp: int = 0) -> np.ndarray:
+    """float32 audio at the noise blanker's input.  `kind`: "voiced", a low-order resonator
+    y[i] = a1 y[i-1] + a2 y[i-2] + e driven by white noise e of `sigma` (counter-based, `seed`);
+    "tone", a sine of `tone` Hz and `amplitude` plus that noise; "noise", the noise alone; "dc",
+    `amplitude` everywhere; "silence".  `impulses`: (position, amplitude) pairs added on top, one
+    sample each.  The first `ramp` samples fade in under a raised cosine.  The sum is multiplied by
+    `scale` in double and rounded to float32; then the sample at `nan_at` becomes a NaN and the one at
+    `inf_at` an infinity."""
+    e = sigma * _noise(np.array([4 << 16 | seed], np.int64), 0, nsamples, 1.0)[0][0]
+    if kind == "voiced":
+        y = np.zeros(nsamples)
+        y1 = y2 = 0.0
+        for i in range(nsamples):
+            y[i] = a1 * y1 + a2 * y2 + e[i]
+            y2, y1 = y1, y[i]
+    elif kind == "tone":
+        y = amplitude * np.sin(2.0 * np.pi * tone * np.arange(nsamples) / rate) + e
+    elif kind == "noise":
+        y = e.copy()
+    elif kind == "dc":
+        y = np.full(nsamples, float(amplitude))
+    elif kind == "silence":
+        y = np.zeros(nsamples)
+    else:
+        raise ValueError(f"nb_audio: kind {kind!r}")
+    for pos, amp in impulses:
+        y[int(pos)] += float(amp)
+    if ramp > 0:
+        y[:ramp] *= 0.5 - 0.5 * np.cos(np.pi * np.arange(min(ramp, nsamples)) / ramp)
+    x = (y * scale).astype(np.float32)
+    if nan_at >= 0:
+        x[nan_at] = np.float32("nan")
+    if inf_at >= 0:
+        x[inf_at] = np.float32("inf")
+    return x
+
+
+def nb_fixture(path: str) -> dict:
+    """A recorded noise-blanker case (an npz of tools/nb/make_nb_golden.py) with its input regenerated
+    from the recorded arguments of nb_audio and checked against the recorded crc32: the file's arrays
+    plus `audio` (float32, read-only) and `cfg` (the settings as a dict)."""
+    import json
+    import zlib
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    audio = nb_audio(**json.loads(str(g["gen"])))
+    if len(audio) != int(g["samples"]) or zlib.crc32(audio.tobytes()) != int(g["crc32"]):
+        raise ValueError(f"{path}: regenerated input differs from the recorded one")
+    audio.setflags(write=False)
+    g["audio"] = audio
+    g["cfg"] = json.loads(str(g["config"]))
+    return g
