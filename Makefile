@@ -4,6 +4,8 @@
 #                      oracle/build/libuhsdr_oracle.so (test infrastructure: CPU restatement)
 #                      tests/build/libuhsdr_libm_probe{,_host}.so, libuhsdr_expf_probe{,_host}.so (test-only libm probes)
 #   make ref        -> oracle/_ref/uhsdr_ref          (reference firmware chain, needs /root/reference)
+#   make fixtures-check -> every module fixture under tests/golden re-recorded from the reference and compared (needs it too)
+#   make sanitize   -> tests/build/sanitize/: the modules' host code under ASan / UBSan (tools/sanitize.mk; CPU only)
 #
 # Host C is compiled without FP contraction and without -march, like the reference build,
 # so every binary32 rounding of the setup math and of the oracle matches the reference.
@@ -82,10 +84,20 @@ $(EXAMPLE): examples/rx_batch.c include/uhsdr.h $(LIB) | examples/build
 ref:
 	$(MAKE) -C oracle/ref
 
+# re-record every module fixture from the reference (tools/recording.py) and the two generated
+# table headers, and fail where a committed file would change; nothing is written
+MAKERS := cwtext rtty psk digimod cwgen nr nb
+fixtures-check:
+	set -e; for m in $(MAKERS); do python3 tools/$$m/make_$${m}_golden.py --check; done
+	python3 tools/cwgen/gen_cwgen_tables.py --check
+	python3 tools/nr/gen_nr_tables.py --check
+
+include tools/sanitize.mk
+
 clean:
 	rm -rf $(OBJDIR) uhsdr_amd/lib oracle/build examples/build tests/build
 
-.PHONY: all ref clean
+.PHONY: all ref fixtures-check clean
 
 # compile-time variants of libuhsdr_amd.so for A/B measurement (bench.py with UHSDR_LIB=<path>):
 #   make variant VTAG=trace VFLAGS=-DUHSDR_TRACE

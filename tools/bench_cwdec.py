@@ -9,15 +9,12 @@ Prints one JSON line: ms per call and ns per channel-block, timed with device ev
 calls after one warm-up pass, plus the host decoder's rate on one thread for scale."""
 import argparse
 import glob
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import ROOT, emit, rows_on_device, timed_second_pass
 
 
 def main():
@@ -33,30 +30,25 @@ def main():
     need = a.blocks * a.calls
     rows = np.stack([np.resize(s, need) for s in cases])
     C = a.channels
-    state = torch.from_numpy(rows).cuda().repeat((C + len(rows) - 1) // len(rows), 1)[:C].contiguous()
+    state = rows_on_device(torch, rows, C)
     pieces = [state[:, k * a.blocks:(k + 1) * a.blocks].contiguous() for k in range(a.calls)]
     del state
     s = torch.cuda.current_stream()
     dec = cwdec.CwDecoder(C, 88, 0, 64, stream=s.cuda_stream)
-    ms = []
-    for rep in range(2):                       # pass 0 warms up
-        dec.reset()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
+
+    def run():
         for p in pieces:
             dec.process(p)
-        e1.record(s)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / a.calls)
+    ms = timed_second_pass(torch, dec.reset, run, a.calls)
     chars = int(dec.read()[1].astype(np.int64).sum())
     host = cwdec.CwDecoder(len(rows), 88, 0, 64, host=True)
     t0 = time.perf_counter()
     host.process(np.ascontiguousarray(rows))
     host_ns = (time.perf_counter() - t0) * 1e9 / rows.size
-    print(json.dumps({"workload": "cw_decode: Morse-to-text, fixture streams tiled over the lanes", "channels": C,
-                      "blocks_per_call": a.blocks, "calls": a.calls, "ms_per_call": round(ms[1], 4),
-                      "ns_per_channel_block": round(ms[1] * 1e6 / (C * a.blocks), 4),
-                      "characters": chars, "host_ns_per_channel_block_1_thread": round(host_ns, 1)}))
+    emit({"workload": "cw_decode: Morse-to-text, fixture streams tiled over the lanes", "channels": C,
+          "blocks_per_call": a.blocks, "calls": a.calls, "ms_per_call": round(ms, 4),
+          "ns_per_channel_block": round(ms * 1e6 / (C * a.blocks), 4),
+          "characters": chars, "host_ns_per_channel_block_1_thread": round(host_ns, 1)})
 
 
 if __name__ == "__main__":

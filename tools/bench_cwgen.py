@@ -10,15 +10,11 @@ Prints one JSON line per channel count: ms per call, channel-samples per second 
 bytes per second, timed with device events over the calls after one warm-up pass, plus the host
 generator's rate on one thread for scale."""
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import emit, timed_second_pass
 
 TEXTS = [b"CQ CQ DE UHSDR K", b"5NN TU 73", b"the quick brown fox", b"QRZ? PSE AGN", b"", b""]
 
@@ -51,25 +47,23 @@ def main():
         keys = torch.from_numpy(keys_for(C, blocks)).cuda()
         i = torch.zeros((C, a.samples), dtype=torch.float32, device="cuda")
         q = torch.zeros_like(i)
-        ms = []
-        for rep in range(2):                       # pass 0 warms up
+
+        def prepare():
             gen.reset()
             gen.put_text(texts)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
+
+        def run():
             for _ in range(a.calls):
                 gen.process(keys, i, q)
-            e1.record(s)
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.calls)
+        ms = timed_second_pass(torch, prepare, run, a.calls)
         active = float((gen.flags() & 1).mean())
         took = int(gen.consumed().astype(np.int64).sum())
         gen.close()
         del i, q, keys
-        print(json.dumps(dict(bench="cwgen", channels=C, samples=a.samples, calls=a.calls, ms_per_call=round(ms[1], 4),
-                              channel_samples_per_s=round(C * a.samples / ms[1] * 1e3), out_gbytes_per_s=round(8 * C * a.samples / ms[1] / 1e6, 2),
-                              realtime_channels=round(C * a.samples / ms[1] * 1e3 / 48000), keyed_fraction_last_call=round(active, 3),
-                              characters_taken=took, host_samples_per_s=round(host_rate))), flush=True)
+        emit(dict(bench="cwgen", channels=C, samples=a.samples, calls=a.calls, ms_per_call=round(ms, 4),
+                  channel_samples_per_s=round(C * a.samples / ms * 1e3), out_gbytes_per_s=round(8 * C * a.samples / ms / 1e6, 2),
+                  realtime_channels=round(C * a.samples / ms * 1e3 / 48000), keyed_fraction_last_call=round(active, 3),
+                  characters_taken=took, host_samples_per_s=round(host_rate)))
 
 
 if __name__ == "__main__":

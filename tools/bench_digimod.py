@@ -10,15 +10,11 @@ Prints one JSON line per modulator and channel count: ms per call, channel-sampl
 the output's bytes per second, timed with device events over the calls after one warm-up pass, plus
 the host modulator's rate on one thread for scale."""
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import emit, timed_second_pass
 
 TEXTS = [b"RYRY CQ DE UHSDR K", b"A1B2C3-D4?E5", b"the quick brown fox 0123456789", b"CQ CQ de UHSDR, Pse k (QSL?) #7", b"599 73\r\n", b""]
 
@@ -30,20 +26,15 @@ def make(kind, channels, host=False, stream=None):
     return digimod.PskModulator(channels, psk.SPEED_125, capacity=64, host=host, stream=stream)
 
 
-def timed(mod, audio, calls, texts, stream):
-    import torch
-    ms = []
-    for rep in range(2):                       # pass 0 warms up
+def timed(torch, mod, audio, calls, texts):
+    def prepare():
         mod.reset()
         mod.put_text(texts)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
+
+    def run():
         for _ in range(calls):
             mod.process(audio)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / calls)
-    return ms[1]
+    return timed_second_pass(torch, prepare, run, calls)
 
 
 def main():
@@ -65,14 +56,14 @@ def main():
             texts = [TEXTS[c % len(TEXTS)] for c in range(C)]
             mod = make(kind, C, stream=s.cuda_stream)
             audio = torch.zeros((C, a.samples), dtype=torch.int16, device="cuda")
-            ms = timed(mod, audio, a.calls, texts, s)
+            ms = timed(torch, mod, audio, a.calls, texts)
             took = int(mod.consumed().astype(np.int64).sum())
             mod.close()
             del audio
-            print(json.dumps(dict(bench="digimod", kind=kind, channels=C, samples=a.samples, calls=a.calls, ms_per_call=round(ms, 4),
-                                  channel_samples_per_s=round(C * a.samples / ms * 1e3), out_gbytes_per_s=round(2 * C * a.samples / ms / 1e6, 2),
-                                  realtime_channels=round(C * a.samples / ms * 1e3 / 48000), characters_taken=took,
-                                  host_samples_per_s=round(host_rate))), flush=True)
+            emit(dict(bench="digimod", kind=kind, channels=C, samples=a.samples, calls=a.calls, ms_per_call=round(ms, 4),
+                      channel_samples_per_s=round(C * a.samples / ms * 1e3), out_gbytes_per_s=round(2 * C * a.samples / ms / 1e6, 2),
+                      realtime_channels=round(C * a.samples / ms * 1e3 / 48000), characters_taken=took,
+                      host_samples_per_s=round(host_rate)))
 
 
 if __name__ == "__main__":

@@ -13,34 +13,12 @@ for the blanker the share of channels (lanes) that repaired at least one place i
 and the places repaired per channel-frame: repairs are divergent work.  --out appends the lines to
 a file."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import emit, rows_on_device, timed
+
 WARMUP = 24
-
-
-def rows_on_device(torch, base, channels):
-    t = torch.from_numpy(np.ascontiguousarray(base)).cuda()
-    return t.repeat((channels + len(base) - 1) // len(base), 1)[:channels].contiguous()
-
-
-def timed(torch, call, calls):
-    for _ in range(WARMUP):
-        call()
-    torch.cuda.synchronize()
-    s = torch.cuda.current_stream()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    for _ in range(calls):
-        call()
-    e1.record(s)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def main():
@@ -64,18 +42,12 @@ def main():
         imp = [[int(p), float(rng.uniform(20000, 30000) * rng.choice([-1, 1]))] for p in at[at < n]] if k % 2 else []
         base.append(synth.nb_audio(n, seed=k, impulses=imp))
     base = np.stack(base)
-    lines = []
-
-    def emit(line):
-        lines.append(line)
-        print(json.dumps(line), flush=True)
-
     for C in [int(c) for c in a.channels.split(",")]:
         x = rows_on_device(torch, base, C)
         y = torch.empty_like(x)
         for run in range(a.runs):
             p = nb.NbProcessor(C, nb.nb_config(nb_setting=a.setting), stream=s.cuda_stream)
-            ms = timed(torch, lambda: p.process_frames(x, y), a.calls)
+            ms = timed(torch, lambda: p.process_frames(x, y), a.calls, WARMUP)
             before = p.state()[1].astype(np.int64)
             p.process_frames(x, y)
             places = p.state()[1].astype(np.int64) - before
@@ -85,21 +57,17 @@ def main():
                   "ms_per_call": round(ms, 4), "frames_per_s": round(C * F / (ms * 1e-3), 0),
                   "ns_per_channel_frame": round(ms * 1e6 / (C * F), 3),
                   "lanes_repairing_share": round(float((places > 0).mean()), 4),
-                  "places_per_channel_frame": round(float(places.sum()) / (C * F), 4)})
+                  "places_per_channel_frame": round(float(places.sum()) / (C * F), 4)}, a.out)
         for level, kw in (("stream_nr", dict()), ("stream_nb_nr", dict(nb_setting=a.setting)), ("stream_nb", dict(nb_setting=a.setting, nr_bypass=1))):
             for run in range(a.runs):
                 p = nr.NrProcessor(C, nr.nr_config(width_hz=3200, offset_hz=1700, **kw), stream=s.cuda_stream)
-                ms = timed(torch, lambda: p.process(x, y), a.calls)
+                ms = timed(torch, lambda: p.process(x, y), a.calls, WARMUP)
                 p.close()
                 emit({"workload": f"12 ksps stream at 3200 Hz, {n} samples ({F} frames) a call: {level}", "level": level, "channels": C,
                       "frames_per_call": F, "calls": a.calls, "warmup_calls": WARMUP, "run": run, "ms_per_call": round(ms, 4),
-                      "frames_per_s": round(C * F / (ms * 1e-3), 0), "ns_per_channel_frame": round(ms * 1e6 / (C * F), 3)})
+                      "frames_per_s": round(C * F / (ms * 1e-3), 0), "ns_per_channel_frame": round(ms * 1e6 / (C * F), 3)}, a.out)
         del x, y
         torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":

@@ -11,34 +11,12 @@ Prints one JSON line per run and level: ms per call and frames per second, timed
 over the calls after a warm-up of 24 calls (past the 20-frame start-up, so the timed calls run the
 noise reduction proper); --out appends the lines to a file."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import emit, rows_on_device, timed
+
 WARMUP = 24
-
-
-def rows_on_device(torch, base, channels):
-    t = torch.from_numpy(np.ascontiguousarray(base)).cuda()
-    return t.repeat((channels + len(base) - 1) // len(base), 1)[:channels].contiguous()
-
-
-def timed(torch, call, calls):
-    for _ in range(WARMUP):
-        call()
-    torch.cuda.synchronize()
-    s = torch.cuda.current_stream()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    for _ in range(calls):
-        call()
-    e1.record(s)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def main():
@@ -53,7 +31,6 @@ def main():
     from uhsdr_amd import nr, synth
     C, F = a.channels, a.frames
     s = torch.cuda.current_stream()
-    lines = []
     for level, n, rate in (("frames", F * nr.FRAME, 6000.0), ("stream", 2 * F * nr.FRAME, 12000.0)):
         base = np.stack([synth.nr_audio(n, rate=rate, snr_db=-3.0 + 0.36 * k, seed=k) for k in range(64)])
         x = rows_on_device(torch, base, C)
@@ -61,22 +38,17 @@ def main():
         for run in range(a.runs):
             p = nr.NrProcessor(C, nr.nr_config(), stream=s.cuda_stream)
             call = (lambda: p.process_frames(x, y)) if level == "frames" else (lambda: p.process(x, y))
-            ms = timed(torch, call, a.calls)
+            ms = timed(torch, call, a.calls, WARMUP)
             nn = p.state()[1]
             p.close()
-            lines.append({"workload": f"nr {level}: {F} frames of 128 samples a call at 6 ksps, signals in noise tiled over the channels",
-                          "level": level, "channels": C, "frames_per_call": F, "calls": a.calls, "warmup_calls": WARMUP, "run": run,
-                          "ms_per_call": round(ms, 4), "frames_per_s": round(C * F / (ms * 1e-3), 0),
-                          "ns_per_channel_frame": round(ms * 1e6 / (C * F), 3),
-                          "realtime_channels_at_6ksps": round(C * F / (ms * 1e-3) / (6000.0 / nr.FRAME), 0),
-                          "nn_values": sorted(set(nn.tolist()))})
-            print(json.dumps(lines[-1]), flush=True)
+            emit({"workload": f"nr {level}: {F} frames of 128 samples a call at 6 ksps, signals in noise tiled over the channels",
+                  "level": level, "channels": C, "frames_per_call": F, "calls": a.calls, "warmup_calls": WARMUP, "run": run,
+                  "ms_per_call": round(ms, 4), "frames_per_s": round(C * F / (ms * 1e-3), 0),
+                  "ns_per_channel_frame": round(ms * 1e6 / (C * F), 3),
+                  "realtime_channels_at_6ksps": round(C * F / (ms * 1e-3) / (6000.0 / nr.FRAME), 0),
+                  "nn_values": sorted(set(nn.tolist()))}, a.out)
         del x, y
         torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":

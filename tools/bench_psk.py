@@ -11,30 +11,19 @@ adds the RTTY decoder's time on the same input in the same process, for context 
 on every sample whatever the data; tools/bench_rtty.py is its own benchmark)."""
 import argparse
 import glob
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import ROOT, emit, rows_on_device, timed_second_pass
 
 
-def timed(dec, pieces, stream):
-    import torch
-    ms = []
-    for rep in range(2):                       # pass 0 warms up
-        dec.reset()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
+def timed(torch, dec, pieces):
+    def run():
         for p in pieces:
             dec.process(p)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / len(pieces))
-    return ms[1]
+    return timed_second_pass(torch, dec.reset, run, len(pieces))
 
 
 def main():
@@ -51,13 +40,10 @@ def main():
     need = a.samples * a.calls
     rows = np.stack([np.resize(s, need) for s in cases])
     C = a.channels
-    pieces = []
-    for k in range(a.calls):
-        p = torch.from_numpy(np.ascontiguousarray(rows[:, k * a.samples:(k + 1) * a.samples])).cuda()
-        pieces.append(p.repeat((C + len(rows) - 1) // len(rows), 1)[:C].contiguous())
+    pieces = [rows_on_device(torch, rows[:, k * a.samples:(k + 1) * a.samples], C) for k in range(a.calls)]
     s = torch.cuda.current_stream()
     dec = psk.PskDecoder(C, psk.SPEED_125, capacity=64, stream=s.cuda_stream)
-    ms = timed(dec, pieces, s)
+    ms = timed(torch, dec, pieces)
     chars = int(dec.read()[1].astype(np.int64).sum())
     host = psk.PskDecoder(len(rows), psk.SPEED_125, capacity=64, host=True)
     t0 = time.perf_counter()
@@ -70,8 +56,8 @@ def main():
            "characters": chars, "host_ns_per_channel_sample_1_thread": round(host_ns, 1)}
     if a.rtty:
         rdec = rtty.RttyDecoder(C, rtty.SHIFT_170, rtty.SPEED_45, rtty.STOP_1_5, 0, capacity=64, stream=s.cuda_stream)
-        out["rtty_ms_per_call_same_process"] = round(timed(rdec, pieces, s), 4)
-    print(json.dumps(out))
+        out["rtty_ms_per_call_same_process"] = round(timed(torch, rdec, pieces), 4)
+    emit(out)
 
 
 if __name__ == "__main__":

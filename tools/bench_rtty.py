@@ -10,15 +10,12 @@ Prints one JSON line: ms per call and channel-samples per second, timed with dev
 the calls after one warm-up pass, plus the host decoder's rate on one thread for scale."""
 import argparse
 import glob
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchlib import ROOT, emit, rows_on_device, timed_second_pass
 
 
 def main():
@@ -35,32 +32,24 @@ def main():
     need = a.samples * a.calls
     rows = np.stack([np.resize(s, need) for s in cases])
     C = a.channels
-    pieces = []
-    for k in range(a.calls):
-        p = torch.from_numpy(np.ascontiguousarray(rows[:, k * a.samples:(k + 1) * a.samples])).cuda()
-        pieces.append(p.repeat((C + len(rows) - 1) // len(rows), 1)[:C].contiguous())
+    pieces = [rows_on_device(torch, rows[:, k * a.samples:(k + 1) * a.samples], C) for k in range(a.calls)]
     s = torch.cuda.current_stream()
     dec = rtty.RttyDecoder(C, *config, capacity=64, stream=s.cuda_stream)
-    ms = []
-    for rep in range(2):                       # pass 0 warms up
-        dec.reset()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
+
+    def run():
         for p in pieces:
             dec.process(p)
-        e1.record(s)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / a.calls)
+    ms = timed_second_pass(torch, dec.reset, run, a.calls)
     chars = int(dec.read()[1].astype(np.int64).sum())
     host = rtty.RttyDecoder(len(rows), *config, capacity=64, host=True)
     t0 = time.perf_counter()
     host.process(np.ascontiguousarray(rows))
     host_ns = (time.perf_counter() - t0) * 1e9 / rows.size
-    print(json.dumps({"workload": "rtty_decode: Baudot-to-text, fixture streams tiled over the lanes", "channels": C,
-                      "samples_per_call": a.samples, "calls": a.calls, "ms_per_call": round(ms[1], 4),
-                      "channel_samples_per_s": round(C * a.samples / (ms[1] * 1e-3), 0),
-                      "ns_per_channel_sample": round(ms[1] * 1e6 / (C * a.samples), 5),
-                      "characters": chars, "host_ns_per_channel_sample_1_thread": round(host_ns, 1)}))
+    emit({"workload": "rtty_decode: Baudot-to-text, fixture streams tiled over the lanes", "channels": C,
+          "samples_per_call": a.samples, "calls": a.calls, "ms_per_call": round(ms, 4),
+          "channel_samples_per_s": round(C * a.samples / (ms * 1e-3), 0),
+          "ns_per_channel_sample": round(ms * 1e6 / (C * a.samples), 5),
+          "characters": chars, "host_ns_per_channel_sample_1_thread": round(host_ns, 1)})
 
 
 if __name__ == "__main__":

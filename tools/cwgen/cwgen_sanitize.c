@@ -1,19 +1,9 @@
 /*
  * Stand-alone driver of uhsdr_cwgen_process_host for a host sanitizer build (no device call):
  *
- *   python3 tools/cwgen/dump_cases.py /tmp/cwgen_cases.bin
- *   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
- *   for f in cwgen digimod; do
- *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
- *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
- *         -c -x hip uhsdr_amd/csrc/uhsdr_$f.hip -o /tmp/$f.o; done
- *   for f in uhsdr_amd/csrc/uhsdr_setup tools/cwgen/cwgen_sanitize uhsdr_amd/csrc/uhsdr_filter_tables; do
- *       gcc -O1 -g $S -ffp-contract=off -Iinclude -c $f.c -o /tmp/$(basename $f).o; done
- *   hipcc -fsanitize=address,undefined /tmp/cwgen.o /tmp/digimod.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o \
- *         /tmp/cwgen_sanitize.o -lm -o /tmp/cwgen_sanitize
- *   /tmp/cwgen_sanitize /tmp/cwgen_cases.bin
+ *   make sanitize          (tools/sanitize.mk: builds cwgen_sanitize and runs it on what dump_cases.py writes)
  *
- * (uhsdr_digimod.hip has the text queue's put.)  File: see dump_cases.py.  Every fixture runs with
+ * (linked with uhsdr_digimod.hip as well, which has the text queue's put.)  File: see dump_cases.py.  Every fixture runs with
  * one call between two events, in calls of 7 blocks as the middle one of three channels, and in
  * calls of one block, on exact-size rows; the block crc32s of I and Q, the flags, the characters
  * taken and the echo are compared.  Then every keyer mode runs with the smallest queue and echo

@@ -32,7 +32,6 @@ A file whose recording has not changed is left as it is; --check fails instead o
 
   python3 tools/cwgen/make_cwgen_golden.py [--check] [--out DIR] [--ref /root/reference/mchf-eclipse]
 """
-import argparse
 import json
 import os
 import subprocess
@@ -42,7 +41,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 WINDOW = 256
 IAM_B, IAM_A, STRAIGHT, ULTIMATE = range(4)
 DIT, DAH, BOTH = 1, 2, 3
@@ -230,45 +230,25 @@ def record_tables(drv, tmp):
     return dict(char_codes=char_codes, char_chars=char_chars, sign_codes=sign_codes, sign_chars=sign_chars, env=env)
 
 
-def same(path, rec):
-    if not os.path.exists(path):
-        return False
-    with np.load(path) as old:
-        return set(old.files) == set(rec) and all(np.array_equal(old[k], rec[k]) for k in rec)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--check", action="store_true", help="fail where a file would change instead of writing it")
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f", os.path.join(ROOT, "tools", "cwgen", "cwgen.mk"),
-                    f"OUT={out}", f"REF={a.ref}", "-j8", "cwgen_driver", "cwtx_driver"], check=True, stdout=subprocess.DEVNULL)
+    a = recording.parse_args()
+    out = recording.build(a, ["cwgen"], ["cwgen_driver", "cwtx_driver"])
     drv = os.path.join(out, "cwgen_driver")
-    changed = []
+    writer = recording.Recorder(a)
     with tempfile.TemporaryDirectory() as tmp:
         recs = [("tables", record_tables(drv, tmp))] + [(c["name"], run_case(drv, c, tmp)) for c in cases()]
         recs += [(c["name"], record_chain(out, c, tmp)) for c in chain_cases()]
         for name, rec in recs:
-            path = os.path.join(a.golden, f"cwgen_{name}.npz")
-            kept = same(path, rec)
+            word = writer.save(f"cwgen_{name}.npz", **rec)
             if name == "tables":
-                print(f"tables: {len(rec['char_codes'])} characters, {len(rec['sign_codes'])} prosigns  {'unchanged' if kept else 'NEW'}")
+                print(f"tables: {len(rec['char_codes'])} characters, {len(rec['sign_codes'])} prosigns  {word}")
             elif name.startswith("chain_"):
                 print(f"{name:18s} {len(rec['flags']):6d} calls  {int((rec['flags'] & 1).sum()):5d} active  consumed {int(rec['consumed']):3d}  "
-                      f"echo {bytes(rec['echo'])!r}  peak iq {int(np.abs(rec['iq_win']).max())}  {'unchanged' if kept else 'NEW'}")
+                      f"echo {bytes(rec['echo'])!r}  peak iq {int(np.abs(rec['iq_win']).max())}  {word}")
             else:
                 print(f"{name:18s} {len(rec['flags']):6d} blocks  {int((rec['flags'] & 1).sum()):5d} with a tone  consumed {int(rec['consumed']):3d}  "
-                      f"accepted {rec['accepted'].tolist()}  echo {bytes(rec['echo'])!r}  {'unchanged' if kept else 'NEW'}")
-            if not kept:
-                changed.append(name)
-                if not a.check:
-                    np.savez_compressed(path, **rec)
-    if a.check and changed:
-        sys.exit(f"recordings differ from the committed files: {changed}")
+                      f"accepted {rec['accepted'].tolist()}  echo {bytes(rec['echo'])!r}  {word}")
+    writer.finish()
 
 
 if __name__ == "__main__":

@@ -1,15 +1,7 @@
 /*
  * Stand-alone driver of uhsdr_cwdec_process_host for a host sanitizer build (no device call):
  *
- *   python3 tools/cwtext/dump_states.py /tmp/cwtext_states.bin
- *   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
- *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
- *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
- *         -c -x hip uhsdr_amd/csrc/uhsdr_cwdec.hip -o /tmp/cwdec.o
- *   gcc -O1 -g $S -ffp-contract=off -Iinclude -c uhsdr_amd/csrc/uhsdr_setup.c uhsdr_amd/csrc/uhsdr_filter_tables.c \
- *         tools/cwtext/cwdec_sanitize.c          (objects into the current directory: run it outside the tree)
- *   hipcc -fsanitize=address,undefined /tmp/cwdec.o uhsdr_setup.o uhsdr_filter_tables.o cwdec_sanitize.o -lm -o /tmp/cwdec_sanitize
- *   /tmp/cwdec_sanitize /tmp/cwtext_states.bin
+ *   make sanitize          (tools/sanitize.mk: builds cwdec_sanitize and runs it on what dump_states.py writes)
  *
  * File: int32 cases; per case int32 blocksize, spikecancel, blocks, nchars, then the state bytes
  * and the expected characters.  Every case runs in one piece and in calls of 1 and 97 blocks, alone

@@ -14,9 +14,8 @@ audio, runs each through the driver and stores, per case:
 
 and cwtext_chartable.npz: CwGen_CharacterIdFunc for every code of 0 to 9 elements.
 
-  python3 tools/cwtext/make_cwtext_golden.py [--out DIR] [--ref /root/reference/mchf-eclipse]
+  python3 tools/cwtext/make_cwtext_golden.py [--check] [--out DIR] [--ref /root/reference/mchf-eclipse]
 """
-import argparse
 import os
 import subprocess
 import sys
@@ -24,8 +23,8 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 from uhsdr_amd.synth import morse_keying  # noqa: E402
 
 RATE = 12000.0
@@ -100,19 +99,14 @@ def cases():
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f",
-                    os.path.join(ROOT, "tools", "cwtext", "cwtext.mk"), f"OUT={out}", f"REF={a.ref}", "-j8", "cwtext"], check=True)
+    a = recording.parse_args()
+    out = recording.build(a, ["cwtext"], ["cwtext"])
     drv = os.path.join(out, "cwtext_driver")
+    writer = recording.Recorder(a)
 
     rows = [l.split() for l in subprocess.run([drv, "table"], check=True, capture_output=True, text=True).stdout.splitlines()]
-    np.savez_compressed(os.path.join(a.golden, "cwtext_chartable.npz"), code=np.array([int(r[0]) for r in rows], dtype=np.uint32),
-                        char=np.array([int(r[1]) for r in rows], dtype=np.uint8))
+    writer.save("cwtext_chartable.npz", code=np.array([int(r[0]) for r in rows], dtype=np.uint32),
+                char=np.array([int(r[1]) for r in rows], dtype=np.uint8))
 
     any_hash = any_corrected = False
     with tempfile.TemporaryDirectory() as tmp:
@@ -138,13 +132,14 @@ def main():
             elif c["name"].startswith(("hand", "spikes", "stuck", "speed", "silence", "mixed")):
                 spelled = c["message"].replace("<AR>", "ar").replace("<SK>", "sk").replace("<KN>", "kn").replace("<HH>", "err")
                 any_corrected |= text.count(spelled.strip()) < c["reps"]
-            np.savez_compressed(os.path.join(a.golden, f"cwtext_{c['name']}.npz"), state=np.array(state, dtype=np.uint8),
-                                blocksize=np.int32(c["blocksize"]), spikecancel=np.int32(c["spikecancel"]),
-                                chars=np.array(chars, dtype=np.uint8), char_block=np.array(char_block, dtype=np.int32),
-                                speed=np.array(speed, dtype=np.uint8), message=np.array(c["message"]),
-                                noisecancel=np.int32(c["noisecancel"]), thresh=np.int32(THRESH))
+            writer.save(f"cwtext_{c['name']}.npz", state=np.array(state, dtype=np.uint8),
+                        blocksize=np.int32(c["blocksize"]), spikecancel=np.int32(c["spikecancel"]),
+                        chars=np.array(chars, dtype=np.uint8), char_block=np.array(char_block, dtype=np.int32),
+                        speed=np.array(speed, dtype=np.uint8), message=np.array(c["message"]),
+                        noisecancel=np.int32(c["noisecancel"]), thresh=np.int32(THRESH))
     assert any_hash, "no case emits '#'"
     assert any_corrected, "no case emits text that differs from what was keyed"
+    writer.finish()
 
 
 if __name__ == "__main__":

@@ -2,16 +2,7 @@
  * Stand-alone driver of uhsdr_rttymod_process_host / uhsdr_pskmod_process_host for a host sanitizer
  * build (no device call):
  *
- *   python3 tools/digimod/dump_cases.py /tmp/digimod_cases.bin
- *   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
- *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
- *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
- *         -c -x hip uhsdr_amd/csrc/uhsdr_digimod.hip -o /tmp/digimod.o
- *   for f in uhsdr_amd/csrc/uhsdr_setup tools/digimod/digimod_sanitize uhsdr_amd/csrc/uhsdr_filter_tables; do
- *       gcc -O1 -g $S -ffp-contract=off -Iinclude -c $f.c -o /tmp/$(basename $f).o; done
- *   hipcc -fsanitize=address,undefined /tmp/digimod.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o \
- *         /tmp/digimod_sanitize.o -lm -o /tmp/digimod_sanitize
- *   /tmp/digimod_sanitize /tmp/digimod_cases.bin
+ *   make sanitize          (tools/sanitize.mk: builds digimod_sanitize and runs it on what dump_cases.py writes)
  *
  * File: see dump_cases.py.  Every fixture runs in one piece, in calls of 97 samples as the middle
  * one of three channels (the other two without text), in calls of 23 and, up to 70000 samples, of 1,

@@ -35,7 +35,6 @@ files byte for byte; --check fails instead of writing where one would change.
 
   python3 tools/digimod/make_digimod_golden.py [--check] [--out DIR] [--ref /root/reference/mchf-eclipse]
 """
-import argparse
 import json
 import os
 import subprocess
@@ -45,7 +44,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 WHOLE = 65536
 BLOCK = 1024
 WINDOW = 256
@@ -220,60 +220,29 @@ def record_chain(out, c, tmp):
                 consumed=np.uint32(consumed), txoff=np.bool_(txoff != 0xffffffff), state=np.uint8(state))
 
 
-def same(path, rec):
-    if not os.path.exists(path):
-        return False
-    with np.load(path) as old:
-        return set(old.files) == set(rec) and all(np.array_equal(old[k], rec[k]) for k in rec)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--check", action="store_true", help="fail where a file would change instead of writing it")
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
+    a = recording.parse_args()
     # the modulators' recorder, and the decoders' (tools/rtty, tools/psk) for the loopback
-    frags = [x for d in ("digimod", "rtty", "psk") for x in ("-f", os.path.join(ROOT, "tools", d, d + ".mk"))]
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", *frags, f"OUT={out}", f"REF={a.ref}", "-j8",
-                    "modgen_driver", "modtx_driver", "rtty", "psk_driver"], check=True, stdout=subprocess.DEVNULL)
+    out = recording.build(a, ["digimod", "rtty", "psk"], ["modgen_driver", "modtx_driver", "rtty", "psk_driver"])
     drv = os.path.join(out, "modgen_driver")
-    changed = []
+    writer = recording.Recorder(a)
     with tempfile.TemporaryDirectory() as tmp:
         for c in cases():
             rec, samples = run_case(drv, c, tmp)
-            path = os.path.join(a.golden, f"digimod_{c['name']}.npz")
-            kept = same(path, rec)
+            word = writer.save(f"digimod_{c['name']}.npz", **rec)
             print(f"{c['name']:18s} {len(samples):8d} samples  consumed {rec['consumed'][-1]:4d}  txoff {int(rec['txoff_at'][-1]):10d}  "
                   f"state {rec['state'][-1]}  accepted {rec['accepted'].tolist()}  peak {int(np.abs(samples.astype(np.int32)).max())}"
-                  f"  {'unchanged' if kept else 'NEW'}")
-            if not kept:
-                changed.append(c["name"])
-                if not a.check:
-                    np.savez_compressed(path, **rec)
+                  f"  {word}")
         for c in loop_cases():
             rec = record_loop(out, drv, c, tmp)
-            path = os.path.join(a.golden, f"digimod_{c['name']}.npz")
-            kept = same(path, rec)
-            print(f"{c['name']:18s} lead {int(rec['lead']):4d}  verbatim {bool(rec['verbatim'])}  {bytes(rec['chars'])!r}  {'unchanged' if kept else 'NEW'}")
-            if not kept:
-                changed.append(c["name"])
-                if not a.check:
-                    np.savez_compressed(path, **rec)
+            word = writer.save(f"digimod_{c['name']}.npz", **rec)
+            print(f"{c['name']:18s} lead {int(rec['lead']):4d}  verbatim {bool(rec['verbatim'])}  {bytes(rec['chars'])!r}  {word}")
         for c in chain_cases():
             rec = record_chain(out, c, tmp)
-            path = os.path.join(a.golden, f"digimod_{c['name']}.npz")
-            kept = same(path, rec)
+            word = writer.save(f"digimod_{c['name']}.npz", **rec)
             print(f"{c['name']:20s} consumed {int(rec['consumed']):3d}  state {int(rec['state'])}  peak iq {int(np.abs(rec['iq_win']).max())}"
-                  f"  {'unchanged' if kept else 'NEW'}")
-            if not kept:
-                changed.append(c["name"])
-                if not a.check:
-                    np.savez_compressed(path, **rec)
-    if a.check and changed:
-        sys.exit(f"recordings differ from the committed files: {changed}")
+                  f"  {word}")
+    writer.finish()
 
 
 if __name__ == "__main__":

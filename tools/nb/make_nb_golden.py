@@ -17,7 +17,6 @@ recording that has not changed leaves its file alone; --check fails where one wo
 
   python3 tools/nb/make_nb_golden.py [--out DIR] [--ref DIR] [--check]
 """
-import argparse
 import json
 import os
 import struct
@@ -28,8 +27,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 from uhsdr_amd import synth  # noqa: E402
 
 FRAME = 128
@@ -98,30 +97,10 @@ def run_starts(mask):
     return np.flatnonzero(m[1:] & ~m[:-1])
 
 
-def save(path, check, **arrays):
-    """write the npz unless the recording is what the file already holds"""
-    if os.path.exists(path):
-        with np.load(path) as z:
-            same = set(z.files) == set(arrays) and all(
-                np.asarray(arrays[k]).dtype == z[k].dtype and np.asarray(arrays[k]).tobytes() == z[k].tobytes() for k in arrays)
-        if same:
-            return
-    if check:
-        sys.exit(f"{path} would change")
-    np.savez_compressed(path, **arrays)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--check", action="store_true")
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f", os.path.join(ROOT, "tools", "nr", "nr.mk"),
-                    "-f", os.path.join(ROOT, "tools", "nb", "nb.mk"), f"OUT={out}", f"REF={a.ref}", "-j8", "nb_driver", "nb_stream"],
-                   check=True, stdout=subprocess.DEVNULL)
+    a = recording.parse_args()
+    out = recording.build(a, ["nr", "nb"], ["nb_driver", "nb_stream"])
+    writer = recording.Recorder(a)
     drv, strm = os.path.join(out, "nb_driver"), os.path.join(out, "nb_stream")
 
     with tempfile.TemporaryDirectory() as tmp:
@@ -154,9 +133,9 @@ def main():
                 assert int(np.isnan(y).sum()) == 1, c["name"]
             else:
                 assert np.isfinite(y).all(), c["name"]
-            save(os.path.join(a.golden, f"nb_{c['name']}.npz"), a.check, gen=np.array(json.dumps(c["gen"])),
-                 config=np.array(json.dumps(dict(nb_setting=c["setting"]))), samples=np.int32(len(x)),
-                 crc32=np.uint32(zlib.crc32(x.tobytes())), out=y)
+            writer.save(f"nb_{c['name']}.npz", gen=np.array(json.dumps(c["gen"])),
+                        config=np.array(json.dumps(dict(nb_setting=c["setting"]))), samples=np.int32(len(x)),
+                        crc32=np.uint32(zlib.crc32(x.tobytes())), out=y)
         assert counts["sparse_s1"] < counts["sparse_s8"] < counts["sparse_s15"], counts
 
         for c in stream_cases():
@@ -176,8 +155,9 @@ def main():
                 assert not y[:256 + DELAY].any() and 0 < ch.sum() <= 7 * 5 * (len(x) // FRAME), c["name"]
             else:
                 assert first >= (256 if cfg["width_hz"] >= 2701 else 512), c["name"]
-            save(os.path.join(a.golden, f"nb_stream_{c['name']}.npz"), a.check, gen=np.array(json.dumps(c["gen"])),
-                 config=np.array(json.dumps(cfg)), samples=np.int32(len(x)), crc32=np.uint32(zlib.crc32(x.tobytes())), out=y)
+            writer.save(f"nb_stream_{c['name']}.npz", gen=np.array(json.dumps(c["gen"])),
+                        config=np.array(json.dumps(cfg)), samples=np.int32(len(x)), crc32=np.uint32(zlib.crc32(x.tobytes())), out=y)
+    writer.finish()
 
 
 if __name__ == "__main__":

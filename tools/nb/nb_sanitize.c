@@ -2,10 +2,7 @@
  * Stand-alone driver of the noise blanker's host step functions (uhsdr_amd/csrc/uhsdr_nb.h, the text
  * the nb_frames kernel runs) for a host sanitizer build; plain C, no device call:
  *
- *   python3 tools/nb/dump_cases.py /tmp/nb_cases.bin
- *   gcc -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off \
- *       -Iuhsdr_amd/csrc tools/nb/nb_sanitize.c -lm -o /tmp/nb_sanitize
- *   /tmp/nb_sanitize /tmp/nb_cases.bin
+ *   make sanitize          (tools/sanitize.mk: builds nb_sanitize and runs it on what dump_cases.py writes)
  *
  * File: see dump_cases.py.  Every frame case runs on a working buffer and a filtered frame that are
  * heap blocks of exactly 154 and 128 floats (so a step outside them is seen), once with the samples

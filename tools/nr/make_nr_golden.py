@@ -19,7 +19,6 @@ and asserts what each case is there to show.  A recording that has not changed l
 
   python3 tools/nr/make_nr_golden.py [--out DIR] [--ref DIR] [--check]
 """
-import argparse
 import json
 import os
 import struct
@@ -30,8 +29,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 from uhsdr_amd import synth  # noqa: E402
 
 FRAME = 128
@@ -97,32 +96,10 @@ def band(cfg):
     return int(lf) & 255, int(uf) & 255
 
 
-def save(path, check, **arrays):
-    """write the npz unless the recording is what the file already holds"""
-    if os.path.exists(path):
-        with np.load(path) as z:
-            same = set(z.files) == set(arrays) and all(
-                np.asarray(arrays[k]).dtype == z[k].dtype and np.array_equal(np.asarray(arrays[k]).view(np.uint8) if np.asarray(arrays[k]).dtype.kind == "f"
-                                                                             else np.asarray(arrays[k]), z[k].view(np.uint8) if z[k].dtype.kind == "f" else z[k])
-                for k in arrays)
-        if same:
-            return
-    if check:
-        sys.exit(f"{path} would change")
-    np.savez_compressed(path, **arrays)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--check", action="store_true")
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f",
-                    os.path.join(ROOT, "tools", "nr", "nr.mk"), f"OUT={out}", f"REF={a.ref}", "-j8", "nr_driver", "nr_stream"],
-                   check=True, stdout=subprocess.DEVNULL)
+    a = recording.parse_args()
+    out = recording.build(a, ["nr"], ["nr_driver", "nr_stream"])
+    writer = recording.Recorder(a)
     drv, strm = os.path.join(out, "nr_driver"), os.path.join(out, "nr_stream")
 
     with tempfile.TemporaryDirectory() as tmp:
@@ -133,7 +110,7 @@ def main():
         subprocess.run([strm, "tables", fout], check=True)
         fir = np.fromfile(fout, dtype=np.float32)
         assert len(window) == 256 and len(fir) == 44
-        save(os.path.join(a.golden, "nr_tables.npz"), a.check, sqrt_hann_256=window, decimate=fir[:4].copy(), interpolate=fir[4:].copy())
+        writer.save("nr_tables.npz", sqrt_hann_256=window, decimate=fir[:4].copy(), interpolate=fir[4:].copy())
 
         # inverse transform vectors: an impulse, a spectrum with conjugate symmetry, random complex
         # values without it, one bin alone, and values spread over 60 decades with a negative zero
@@ -150,7 +127,7 @@ def main():
         xin = np.ascontiguousarray(x).view(np.float32).reshape(5, 512)
         xin.tofile(fin)
         subprocess.run([drv, "icfft", fin, fout], check=True)
-        save(os.path.join(a.golden, "nr_icfft.npz"), a.check, x=xin.copy(), y=np.fromfile(fout, dtype=np.float32).reshape(5, 512))
+        writer.save("nr_icfft.npz", x=xin.copy(), y=np.fromfile(fout, dtype=np.float32).reshape(5, 512))
 
         for c in frame_cases():
             audio = synth.nr_audio(**c["gen"])
@@ -195,7 +172,7 @@ def main():
             else:
                 arrays["out_crc"] = np.array([zlib.crc32(f.tobytes()) for f in y], dtype=np.uint32)
                 arrays["out_head"], arrays["out_tail"] = y[:8].copy(), y[-8:].copy()
-            save(os.path.join(a.golden, f"nr_{c['name']}.npz"), a.check, **arrays)
+            writer.save(f"nr_{c['name']}.npz", **arrays)
 
         for c in stream_cases():
             audio = synth.nr_audio(**c["gen"])
@@ -210,8 +187,9 @@ def main():
             decimated = cfg["width_hz"] < 2701
             print(f"stream_{c['name']:15s} {len(audio):6d} samples  first output at {first}")
             assert (first >= 512 and first < 540) if decimated else first == 257, c["name"]
-            save(os.path.join(a.golden, f"nr_stream_{c['name']}.npz"), a.check, gen=np.array(json.dumps(c["gen"])),
-                 config=np.array(json.dumps(cfg)), samples=np.int32(len(audio)), crc32=np.uint32(zlib.crc32(audio.tobytes())), out=y)
+            writer.save(f"nr_stream_{c['name']}.npz", gen=np.array(json.dumps(c["gen"])),
+                        config=np.array(json.dumps(cfg)), samples=np.int32(len(audio)), crc32=np.uint32(zlib.crc32(audio.tobytes())), out=y)
+    writer.finish()
 
 
 if __name__ == "__main__":

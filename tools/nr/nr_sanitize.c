@@ -2,17 +2,7 @@
  * Stand-alone driver of uhsdr_nr_process_frames_host / uhsdr_nr_process_host for a host sanitizer
  * build (no device call):
  *
- *   python3 tools/nr/dump_cases.py /tmp/nr_cases.bin
- *   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
- *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
- *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
- *         -c -x hip uhsdr_amd/csrc/uhsdr_nr.hip -o /tmp/nr.o
- *   (the same line for uhsdr_amd/csrc/uhsdr_nb.hip -> /tmp/nb.o: the stream can hold a noise blanker)
- *   for f in uhsdr_amd/csrc/uhsdr_setup tools/nr/nr_sanitize uhsdr_amd/csrc/uhsdr_filter_tables; do
- *       gcc -O1 -g $S -ffp-contract=off -Iinclude -c $f.c -o /tmp/$(basename $f).o; done
- *   hipcc -fsanitize=address,undefined /tmp/nr.o /tmp/nb.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o /tmp/nr_sanitize.o \
- *         -lm -o /tmp/nr_sanitize
- *   /tmp/nr_sanitize /tmp/nr_cases.bin
+ *   make sanitize          (tools/sanitize.mk: builds nr_sanitize and runs it on what dump_cases.py writes)
  *
  * File: see dump_cases.py.  Every frame case runs in one piece and in calls of 1, 3 and 21 frames,
  * alone and as one of three channels on rows longer than the run; every stream case in one piece and

@@ -27,9 +27,8 @@ with the reference harness and its main, run with mode=6 on a 12 ksps path), per
   chars, char_sample        as above, char_sample counting tap samples
   speed_idx; message        printed verbatim (asserted here)
 
-  python3 tools/psk/make_psk_golden.py [--out DIR] [--ref /root/reference/mchf-eclipse]
+  python3 tools/psk/make_psk_golden.py [--check] [--out DIR] [--ref /root/reference/mchf-eclipse]
 """
-import argparse
 import json
 import os
 import subprocess
@@ -39,8 +38,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 from uhsdr_amd import synth  # noqa: E402
 
 M31 = b"Hello de DL1ABC: 599, 73!"
@@ -101,7 +100,7 @@ def parse(res):
     return np.array(res[1::2], dtype=np.int64).astype(np.uint8), np.array(res[0::2], dtype=np.int32)
 
 
-def record_chain(out, golden, tmp):
+def record_chain(out, writer, tmp):
     rec = os.path.join(out, "psk_chain")
     for c in chain_cases():
         gen = chain_gen(c)
@@ -117,9 +116,9 @@ def record_chain(out, golden, tmp):
         print(f"{c['name']:18s} {len(iq):7d} frames   {text!r}")
         assert c["text"].encode() in text, f"{c['name']}: the reference did not print the message verbatim"
         tap_crc = np.array([zlib.crc32(tap[k:k + 8].tobytes()) for k in range(0, len(tap), 8)], dtype=np.uint32)
-        np.savez_compressed(os.path.join(golden, f"psk_{c['name']}.npz"), gen=np.array(json.dumps(gen)), path=np.int32(c["path"]),
-                            crc32=np.uint32(zlib.crc32(iq.tobytes())), tap_crc=tap_crc, tap_head=tap[:256].copy(),
-                            speed_idx=np.int32(c["speed_idx"]), chars=chars, char_sample=char_sample, message=np.array(c["text"]))
+        writer.save(f"psk_{c['name']}.npz", gen=np.array(json.dumps(gen)), path=np.int32(c["path"]),
+                    crc32=np.uint32(zlib.crc32(iq.tobytes())), tap_crc=tap_crc, tap_head=tap[:256].copy(),
+                    speed_idx=np.int32(c["speed_idx"]), chars=chars, char_sample=char_sample, message=np.array(c["text"]))
 
 
 def check_expectation(name, expect, min_chars, sent, printed):
@@ -136,19 +135,13 @@ def check_expectation(name, expect, min_chars, sent, printed):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f",
-                    os.path.join(ROOT, "tools", "psk", "psk.mk"), f"OUT={out}", f"REF={a.ref}", "-j8", "psk_driver", "psk_chain"],
-                   check=True, stdout=subprocess.DEVNULL)
+    a = recording.parse_args()
+    out = recording.build(a, ["psk"], ["psk_driver", "psk_chain"])
     drv = os.path.join(out, "psk_driver")
+    writer = recording.Recorder(a)
 
     with tempfile.TemporaryDirectory() as tmp:
-        record_chain(out, a.golden, tmp)
+        record_chain(out, writer, tmp)
         for c in cases():
             audio = synth.psk_audio(c["message"], **c["gen"])
             wav = os.path.join(tmp, c["name"] + ".f32")
@@ -157,10 +150,11 @@ def main():
             printed = bytes(chars)
             print(f"{c['name']:14s} {len(audio):7d} samples {len(printed):4d} bytes  {printed[:100]!r}")
             check_expectation(c["name"], c["expect"], c["min_chars"], c["message"], printed)
-            np.savez_compressed(os.path.join(a.golden, f"psk_{c['name']}.npz"), gen=np.array(json.dumps(c["gen"])),
-                                message=np.frombuffer(c["message"], np.uint8), samples=np.int32(len(audio)),
-                                crc32=np.uint32(zlib.crc32(audio.tobytes())), speed_idx=np.int32(c["speed_idx"]),
-                                chars=chars, char_sample=char_sample, expect=np.array(c["expect"]), min_chars=np.int32(c["min_chars"]))
+            writer.save(f"psk_{c['name']}.npz", gen=np.array(json.dumps(c["gen"])),
+                        message=np.frombuffer(c["message"], np.uint8), samples=np.int32(len(audio)),
+                        crc32=np.uint32(zlib.crc32(audio.tobytes())), speed_idx=np.int32(c["speed_idx"]),
+                        chars=chars, char_sample=char_sample, expect=np.array(c["expect"]), min_chars=np.int32(c["min_chars"]))
+    writer.finish()
 
 
 if __name__ == "__main__":

@@ -24,9 +24,8 @@ with the reference harness and its main, run with mode=6 on a 12 ksps path), per
   chars, char_sample        as above, char_sample counting tap samples
   shift_idx, ...            rtty_ctrl_config; message: printed verbatim (asserted here)
 
-  python3 tools/rtty/make_rtty_golden.py [--out DIR] [--ref /root/reference/mchf-eclipse]
+  python3 tools/rtty/make_rtty_golden.py [--check] [--out DIR] [--ref /root/reference/mchf-eclipse]
 """
-import argparse
 import json
 import os
 import subprocess
@@ -36,8 +35,8 @@ import zlib
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recording  # noqa: E402
 from uhsdr_amd import synth  # noqa: E402
 
 M1 = "RYRYRY CQ CQ DE UHSDR UHSDR K"
@@ -111,7 +110,7 @@ def chain_iq(gen):
     return np.ascontiguousarray(synth.rtty_iq([g.pop("channel")], 0, g.pop("nframes"), g.pop("text"), **g)[0], dtype=np.int32)
 
 
-def record_chain(out, golden, tmp):
+def record_chain(out, writer, tmp):
     rec = os.path.join(out, "rtty_chain")
     for c in chain_cases():
         gen = chain_gen(c)
@@ -130,11 +129,11 @@ def record_chain(out, golden, tmp):
         print(f"{c['name']:18s} {len(iq):7d} frames   {text!r}")
         assert CHAIN_MSG in text, f"{c['name']}: the reference did not print the message verbatim"
         tap_crc = np.array([zlib.crc32(tap[k:k + 8].tobytes()) for k in range(0, len(tap), 8)], dtype=np.uint32)
-        np.savez_compressed(os.path.join(golden, f"rtty_{c['name']}.npz"), gen=np.array(json.dumps(gen)), path=np.int32(c["path"]),
-                            crc32=np.uint32(zlib.crc32(iq.tobytes())), tap_crc=tap_crc, tap_head=tap[:256].copy(),
-                            shift_idx=np.int32(c["shift_idx"]), speed_idx=np.int32(c["speed_idx"]),
-                            stopbits_idx=np.int32(c["stopbits_idx"]), atc_disable=np.int32(c["atc_disable"]), chars=chars,
-                            char_sample=char_sample, message=np.array(CHAIN_MSG))
+        writer.save(f"rtty_{c['name']}.npz", gen=np.array(json.dumps(gen)), path=np.int32(c["path"]),
+                    crc32=np.uint32(zlib.crc32(iq.tobytes())), tap_crc=tap_crc, tap_head=tap[:256].copy(),
+                    shift_idx=np.int32(c["shift_idx"]), speed_idx=np.int32(c["speed_idx"]),
+                    stopbits_idx=np.int32(c["stopbits_idx"]), atc_disable=np.int32(c["atc_disable"]), chars=chars,
+                    char_sample=char_sample, message=np.array(CHAIN_MSG))
 
 
 def audio_of(c):
@@ -142,20 +141,14 @@ def audio_of(c):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "oracle", "_ref"), help="build directory (git-ignored or outside)")
-    ap.add_argument("--ref", default="/root/reference/mchf-eclipse")
-    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden"))
-    a = ap.parse_args()
-    out = os.path.abspath(a.out)
-    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", "-f",
-                    os.path.join(ROOT, "tools", "rtty", "rtty.mk"), f"OUT={out}", f"REF={a.ref}", "-j8", "rtty", "rtty_chain"], check=True,
-                   stdout=subprocess.DEVNULL)
+    a = recording.parse_args()
+    out = recording.build(a, ["rtty"], ["rtty", "rtty_chain"])
     drv = os.path.join(out, "rtty_driver")
+    writer = recording.Recorder(a)
 
     resync = False
     with tempfile.TemporaryDirectory() as tmp:
-        record_chain(out, a.golden, tmp)
+        record_chain(out, writer, tmp)
         for c in cases():
             audio = audio_of(c)
             wav = os.path.join(tmp, c["name"] + ".f32")
@@ -174,13 +167,14 @@ def main():
             if c["name"] == "silence":
                 assert len(chars) == 0
             bits = c["bits"] if c["bits"] is not None else (np.zeros(0, np.uint8), np.zeros(0))
-            np.savez_compressed(os.path.join(a.golden, f"rtty_{c['name']}.npz"), gen=np.array(json.dumps(c["gen"])),
-                                bits_level=bits[0], bits_length=bits[1], samples=np.int32(len(audio)),
-                                crc32=np.uint32(zlib.crc32(audio.tobytes())), shift_idx=np.int32(c["shift_idx"]),
-                                speed_idx=np.int32(c["speed_idx"]), stopbits_idx=np.int32(c["stopbits_idx"]),
-                                atc_disable=np.int32(c["atc_disable"]), chars=chars, char_sample=char_sample,
-                                message=np.array(c["message"]), verbatim=np.int32(bool(c["verbatim"])))
+            writer.save(f"rtty_{c['name']}.npz", gen=np.array(json.dumps(c["gen"])),
+                        bits_level=bits[0], bits_length=bits[1], samples=np.int32(len(audio)),
+                        crc32=np.uint32(zlib.crc32(audio.tobytes())), shift_idx=np.int32(c["shift_idx"]),
+                        speed_idx=np.int32(c["speed_idx"]), stopbits_idx=np.int32(c["stopbits_idx"]),
+                        atc_disable=np.int32(c["atc_disable"]), chars=chars, char_sample=char_sample,
+                        message=np.array(c["message"]), verbatim=np.int32(bool(c["verbatim"])))
     assert resync
+    writer.finish()
 
 
 if __name__ == "__main__":

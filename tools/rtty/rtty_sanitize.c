@@ -1,16 +1,7 @@
 /*
  * Stand-alone driver of uhsdr_rtty_process_host for a host sanitizer build (no device call):
  *
- *   python3 tools/rtty/dump_streams.py /tmp/rtty_streams.bin
- *   S="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
- *   hipcc --offload-arch=gfx950 -Iuhsdr_amd/csrc -O1 -g -ffp-contract=off -std=c++17 \
- *         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
- *         -c -x hip uhsdr_amd/csrc/uhsdr_rtty.hip -o /tmp/rtty.o
- *   for f in uhsdr_amd/csrc/uhsdr_setup tools/rtty/rtty_sanitize uhsdr_amd/csrc/uhsdr_filter_tables; do
- *       gcc -O1 -g $S -ffp-contract=off -Iinclude -c $f.c -o /tmp/$(basename $f).o; done
- *   hipcc -fsanitize=address,undefined /tmp/rtty.o /tmp/uhsdr_setup.o /tmp/uhsdr_filter_tables.o /tmp/rtty_sanitize.o \
- *         -lm -o /tmp/rtty_sanitize
- *   /tmp/rtty_sanitize /tmp/rtty_streams.bin
+ *   make sanitize          (tools/sanitize.mk: builds rtty_sanitize and runs it on what dump_streams.py writes)
  *
  * File: see dump_streams.py.  Every case runs in one piece and in calls of 1 and 97 samples, alone
  * and as one of three channels, on exact-size rows, and the text is compared.  Then every
