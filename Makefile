@@ -89,6 +89,7 @@ ref:
 MAKERS := cwtext rtty psk digimod cwgen nr nb
 fixtures-check:
 	set -e; for m in $(MAKERS); do python3 tools/$$m/make_$${m}_golden.py --check; done
+	python3 tools/nr/make_nr_chain_golden.py --check
 	python3 tools/cwgen/gen_cwgen_tables.py --check
 	python3 tools/nr/gen_nr_tables.py --check
 

@@ -1035,8 +1035,8 @@ uhsdr_status uhsdr_cwgen_destroy(uhsdr_cwgen_handle h);
  * process, process_host, process_frames and process_frames_host honour both; reset clears the
  * blanker too; with both 0 every call enqueues exactly what it enqueued before they existed.  With
  * the blanker on, a frame's output lags by 13 samples more.
- * Not built: the LMS noise reduction, the #if 0 notch code, the noise reduction or the blanker
- * inside the RX chain. */
+ * Inside the RX chain: uhsdr_rx_set_nr, at the end of this header.
+ * Not built: the LMS noise reduction, the #if 0 notch code. */
 typedef struct uhsdr_nr_config
 {
     float   alpha;
@@ -1141,8 +1141,8 @@ const char*  uhsdr_rx_kernel_name(int32_t index);
  * the filtered samples 0 .. 12 and a repair lies 10 samples before its hit.  create and reset start
  * from a cleared working buffer, while the firmware never clears its static, not even when the noise
  * reduction restarts (as with the NR's overlap half above).
- * Not built: the old time-domain blanker of audio_driver.c:1278, the blanker inside the RX chain or
- * uhsdr_i2s_*. */
+ * Inside the RX chain: uhsdr_rx_set_nr below.
+ * Not built: the old time-domain blanker of audio_driver.c:1278, the blanker in uhsdr_i2s_*. */
 typedef struct uhsdr_nb_config
 {
     int32_t nb_setting;
@@ -1161,6 +1161,41 @@ uhsdr_status uhsdr_nb_process_frames_host(uhsdr_nb_handle h, const float* in, fl
 uhsdr_status uhsdr_nb_state(uhsdr_nb_handle h, int32_t* last_count, uint32_t* total_count);
 uhsdr_status uhsdr_nb_synchronize(uhsdr_nb_handle h);
 uhsdr_status uhsdr_nb_destroy(uhsdr_nb_handle h);
+
+/* ---- Noise reduction and blanker inside the RX chain ----
+ * The firmware runs both on a_buffer[0] between the AGC and the post-AGC scale whenever the
+ * decimated rate is 12 ksps and DSP NR or the blanker is on (RxProcessor_DemodAudioPostprocessing,
+ * audio_driver.c:2501-2510), so biquad_1, the modems, the CW front end, the interpolator and the
+ * anti-alias lattice see the noise-reduced sample.
+ * set_nr: cfg non-null turns the stage on with a fresh noise reduction and blanker (as
+ * uhsdr_nr_create / uhsdr_nr_reset), owned by the handle; null turns it off and frees it.  cfg is
+ * uhsdr_nr_config as above: nb_setting and nr_bypass select NR alone (0, 0), NB then NR (1 .. 15, 0)
+ * and NB alone (1 .. 15, 1); width_hz and offset_hz state FilterInfo[ts.filters_p->id].width and
+ * ts.filters_p->offset; sample_rate is ignored, as in uhsdr_nr_process (below 2701 Hz the frames run
+ * at 6 ksps).  Every refusal of uhsdr_nr_create is passed on before anything changes, the band judged
+ * at the rate the stream runs.  With the stage on, a call enqueues on the handle's stream: the
+ * front, rx_notch where the plan has one, a head kernel (pre-filter lattice, AGC) that writes
+ * a_buffer[0] to a [C][N/4] row of the handle, uhsdr_nr_process from that row to a second one, a tail
+ * kernel (scale, biquad_1, CW front end, digital-mode tap, interpolator, anti-alias lattice, biquad_2,
+ * the board's output stage), then the text decoders.  With it off, a call enqueues exactly what it
+ * enqueued before the stage existed.  The main loop never falls behind, as in uhsdr_nr_process.
+ * Accepted: a 12 ksps path of the SSB / CW / DIGI back-end family, mono, no DC removal in the AGC,
+ * either board, with or without codec frames, key beep, LMS auto notch, CW front end and CW text,
+ * digital-mode tap, RTTY or BPSK text.  UHSDR_ARGUMENT_ERROR: 24 ksps, AM / SAM, FM and stereo paths,
+ * UHSDR_SCHEDULE_CHAIN, any pipelined mode, FMA precision; and while the stage is on,
+ * uhsdr_rx_set_pipelined(1 .. 3), uhsdr_rx_set_schedule(CHAIN) and uhsdr_rx_set_precision(FMA).
+ * uhsdr_rx_reset resets the stage, uhsdr_rx_destroy frees it, uhsdr_rx_set_stream moves it.
+ * With the stage on, a caller's row for uhsdr_rx_set_digi_tap must be 16-byte aligned, like the audio
+ * rows (the tail kernel stores it in 16-byte pieces); a row that is not gives UHSDR_ARGUMENT_ERROR from
+ * whichever of the two calls comes second.
+ * nr_state: per channel into host arrays of num_channels (null: not wanted), after everything
+ * enqueued: uhsdr_nr_state's three, and uhsdr_nb_state's two (zero with the blanker off).
+ * Not built: the stage in the wave pipeline's pipelined modes, the persistent back end or rx_chain,
+ * on AM / SAM, 24 ksps or stereo paths, in uhsdr_i2s_*, the leaky-LMS noise reduction, a main loop
+ * that falls behind. */
+uhsdr_status uhsdr_rx_set_nr(uhsdr_rx_handle h, const uhsdr_nr_config* cfg);
+uhsdr_status uhsdr_rx_nr_state(uhsdr_rx_handle h, int32_t* first_time, int32_t* nn, float* power_ratio, int32_t* nb_last,
+                               uint32_t* nb_total);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,9 @@ C5's per-GPU share (CW P4 with the CW decoder front end).
 
     python tools/bench_configs.py [--steps K] [--only c3,c4fm,c4tx,c5] > profiles/rNN_configs.jsonl
     (--only c5rtty: DIGI P48 at the C5 shape without and with the RTTY text decoder in the chain;
-     --only c5psk: the same without and with the BPSK text decoder)
+     --only c5psk: the same without and with the BPSK text decoder;
+     --only c5nr: SSB P48 at the C5 shape with the noise reduction stage of uhsdr_rx_set_nr off, with NR
+     alone, and with NB then NR)
 
 One JSON line per workload: Msamples/s of 48 kHz frames, ms per call, per-kernel device ms
 (RX: HIP events on the library stream), algorithmic HBM bytes per frame and the fraction of
@@ -59,7 +61,7 @@ FRONT_BLOCK = 0     # --front-block: the RX lines' front outputs per lane (0 = t
 HANDOFF = "persistent"  # --handoff: the pipelined RX lines' front -> back hand-off (uhsdr_rx_set_pipelined 3 / 2 / 1)
 
 
-def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_text=False, rtty_text=False, psk_text=False):
+def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_text=False, rtty_text=False, psk_text=False, nr=None):
     import torch
     import bench
     import uhsdr_amd as U
@@ -80,6 +82,8 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_te
         chain.set_rtty_text(True, 1, 0, 1, False, 64)   # the RTTY decoder on the N/4 tap samples of each call
     if psk_text:
         chain.set_psk_text(True, 0, 64)                  # the BPSK decoder on the N/4 tap samples of each call
+    if nr is not None:
+        chain.set_nr(nr)                                 # head kernel, the 12 ksps stream, tail kernel
     join = chain.join if pipelined else None
     ms = time_calls(lambda: chain.process(iq, audio, None), steps, warmup, join)
     chain.enable_timing(True)
@@ -104,6 +108,12 @@ def rx_line(name, cfg, C, N, iq, steps, warmup, cw=False, pipelined=False, cw_te
     if psk_text:
         out["psk_text"] = True
         out["psk_text_chars"] = int(chain.psk_text_outputs.read()[1].sum())
+    if nr is not None:
+        # the stage's own traffic is not in alg_bytes_per_frame: two [C][N/4] rows written and read
+        # once each (4 B per frame) plus the stream's work rows and, per 128-sample frame, its state
+        out["nr_stage"] = {"nb_setting": int(nr.nb_setting), "nr_bypass": int(nr.nr_bypass), "width_hz": int(nr.width_hz)}
+        ft = chain.nr_state()[0]
+        out["nr_first_time"] = sorted(set(ft.tolist()))
     chain.close()
     if out["handoff_timeouts"]:
         raise RuntimeError(f"{name}: a device hand-off poll gave up: the line is invalid")
@@ -285,6 +295,16 @@ def main():
         for on in (False, True):
             lines.append(rx_line("C5 shape: DIGI P48" + (" + digital-mode tap + BPSK text (psk_decode)" if on else ""),
                                  cfg, C, N, tiled(gen, C, N), a.steps, a.warmup, psk_text=on))
+    if "c5nr" in want:
+        # SSB P48 at the C5 batch shape in serial mode: the stage off (front + fused back end), NR alone,
+        # NB then NR (front + head + the 12 ksps stream at N/4 samples a call + tail)
+        from uhsdr_amd import nr as nrmod
+        C, N = 1048576 // 8, 256
+        cfg = U.default_config(filter_path=48)
+        iq = tiled(synth.ssb_iq, C, N)
+        for label, stage in (("", None), (" + NR (uhsdr_rx_set_nr)", nrmod.nr_config(width_hz=3800, offset_hz=1900)),
+                             (" + NB then NR (uhsdr_rx_set_nr, nb_setting 8)", nrmod.nr_config(width_hz=3800, offset_hz=1900, nb_setting=8))):
+            lines.append(rx_line("C5 shape: SSB P48" + label, cfg, C, N, iq, a.steps, a.warmup, nr=stage))
     if "c5fir" in want:
         import numpy as np
         C, N = 1048576 // 8, 256

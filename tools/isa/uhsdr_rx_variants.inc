@@ -9,6 +9,7 @@ static const BackVariant kBackFm = { 0, 0, 1, 1, 0, DM_FM, rx_fm<6>, nullptr };
 static const BackVariant kBackStereo[] = { { 10, 6, 4, 1, 49, DM_NONE, nullptr, nullptr } };
 static const NotchVariant kNotch[] = { { 4, DM_NONE, nullptr } };
 static const ChainVariant kChain[] = { CHAIN_V(89, 43, 4, false, 10, 6, 1, 49) };
+static const NrStageVariant kNrStage[] = { NR_V(10, 6, 1, 49) };
 #undef BACK_V
 #undef FRONT_V
 #undef FRONT_ST

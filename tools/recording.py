@@ -31,9 +31,10 @@ def parse_args():
 
 
 def build(args, fragments, targets):
-    """make `targets` by oracle/ref/Makefile plus tools/<m>/<m>.mk for each m of `fragments`; returns the build directory"""
+    """make `targets` by oracle/ref/Makefile plus tools/<m>/<m>.mk for each m of `fragments` (tools/<d>/<f>.mk for one
+    given as "<d>/<f>"); returns the build directory"""
     out = os.path.abspath(args.out)
-    frags = [x for m in fragments for x in ("-f", os.path.join(ROOT, "tools", m, m + ".mk"))]
+    frags = [x for m in fragments for x in ("-f", os.path.join(ROOT, "tools", m + ".mk" if "/" in m else os.path.join(m, m + ".mk")))]
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), "-f", "Makefile", *frags, f"OUT={out}", f"REF={args.ref}", "-j8", *targets],
                    check=True, stdout=subprocess.DEVNULL)
     return out

@@ -346,6 +346,8 @@ SIGNATURES = {
     "uhsdr_nb_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhsdr_nb_synchronize": (C.c_int, [C.c_void_p]),
     "uhsdr_nb_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_rx_set_nr": (C.c_int, [C.c_void_p, C.POINTER(NrConfig)]),
+    "uhsdr_rx_nr_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

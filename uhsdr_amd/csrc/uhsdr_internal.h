@@ -74,6 +74,9 @@ int uhsdr_rx_mode_supported(const uhsdr_rx_plan* p);
 uhsdr_status uhsdr_cwdec_launch(uhsdr_cwdec_handle h, const uint8_t* state, int32_t blocks, int32_t stride,
                                 int32_t offset, int32_t step);
 
+/* the noise blanker a noise reduction handle runs in front (cfg.nb_setting > 0), or null */
+uhsdr_nb_handle uhsdr_nr_blanker(uhsdr_nr_handle h);
+
 /* thread-local last error text for uhsdr_last_error() */
 void uhsdr_set_error(const char* fmt, ...);
 

@@ -844,6 +844,8 @@ extern "C" uhsdr_status uhsdr_nr_state(uhsdr_nr_handle h, int32_t* first_time, i
     return UHSDR_OK;
 }
 
+extern "C" uhsdr_nb_handle uhsdr_nr_blanker(uhsdr_nr_handle h) { return h ? h->nb : nullptr; }
+
 extern "C" uhsdr_status uhsdr_nr_band(const uhsdr_nr_config* cfg, int32_t* vad_low, int32_t* vad_high)
 {
     if (!cfg) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }

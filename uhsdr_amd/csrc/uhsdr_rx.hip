@@ -2806,6 +2806,192 @@ __attribute__((amdgpu_waves_per_eu(FORM == 1 ? fused1_waves(PRE, L) : DM == DM_S
 }
 
 // ------------------------------------------------------------------------------------
+// rx_nr_head / rx_nr_tail: the fused back end cut in two at the place where the firmware runs its
+// noise reduction and blanker (AudioDriver_RxProcessorNoiseReduction on a_buffer[0], audio_driver.c:
+// 2501-2510: after AudioAgc_RunAgcWdsp, before the post-AGC scale), for a handle with
+// uhsdr_rx_set_nr.  The head runs the pre-filter lattice and the AGC and writes a_buffer[0] to a
+// [C][Nd] row; uhsdr_nr_process takes it to a second row; the tail runs the rest of the fused body
+// from that row.  The stage objects, their state arrays and their per-sample arithmetic are the
+// fused body's, lane == channel, one wave per 64 channels; 12 ksps SSB / CW / DIGI back ends only
+// (no demodulator, no DC removal).
+//
+// The rows in HBM: a call is 8 floats (32 B) per channel, and with lane == channel a per-lane access
+// to row[c * Nd + ..] touches 64 lines for 32 useful bytes each.  Both kernels therefore move the
+// rows NR_GROUP = 4 calls at a time through LDS: 32 floats = one 128-byte piece per channel, one row
+// per channel with an odd pitch (FUSED_YPITCH, conflict-free for the lane's own row and for the
+// transposed pass), and lane (g, j) = (lane / 8, lane % 8) moves floats 4j..4j+3 of channels 8k + g,
+// so each global instruction covers 8 whole 128-byte pieces -- fused_store_call's pattern.  A launch
+// of fewer calls, or its last group, moves the shorter piece the same way.
+constexpr int NR_GROUP = 4;
+// Placement of the code object's .text.  The five kernels below come last in it, but their symbols,
+// descriptors and notes lie in front of it and moved every older kernel up by 3840 bytes; C2, whose
+// wave pipeline is bound by one wave's instruction stream, then ran 5 % slower on byte-identical
+// kernels (profiles/r16_placement_ab.jsonl).  These 64 bytes of .rodata make the move 4096 bytes, so
+// every older kernel keeps its address modulo 4 KB, and C2 its rate.  A change that adds kernels or
+// device symbols to this file moves .text again: compare the address of .text with the parent's
+// (llvm-readelf -SW on the unbundled code object, as tools/kres.sh unbundles it) and re-measure C2.
+__device__ __attribute__((used)) const unsigned char uhsdr_rx_text_pad[64] = { 1 };
+
+// floats [0, 8 gc) of every channel's LDS row <-> the rows' floats from call0's first sample
+template <typename F>
+__device__ __forceinline__ void nr_rows_each(const BackArgs& a, const BackLane& l, int call0, int gc, F&& f)
+{
+    const int g = l.lane >> 3, j = l.lane & 7;
+    const int c0 = l.c - l.lane;
+    if (4 * j >= gc * (BLK / 4)) return;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+    {
+        const int cc = 8 * k + g;
+        // uniform base of rows c0 + 8k.. (SGPRs) + the lane's 32-bit offset
+        const size_t rb = (size_t)(c0 + 8 * k) * a.Nd + call0 * (BLK / 4);
+        const unsigned off = (unsigned)g * (unsigned)a.Nd + 4 * j;
+        f(k, cc, c0 + cc, rb, off);
+    }
+}
+
+__device__ __forceinline__ void nr_rows_store(const BackArgs& a, const BackLane& l, int call0, int gc, const float* xs, float* row)
+{
+    wave_sync();                                         // the wave's rows are complete
+    nr_rows_each(a, l, call0, gc, [&](int, int cc, int c, size_t rb, unsigned off)
+    {
+        const float* r = xs + cc * FUSED_YPITCH + 4 * (l.lane & 7);
+        const float4 v = make_float4(r[0], r[1], r[2], r[3]);
+        if (c < a.C) *(float4*)((row + rb) + off) = v;
+    });
+    wave_sync();                                         // rows read before the next group writes
+}
+
+// a channel past the last one takes channel C-1's row (the clamped-load rule)
+__device__ __forceinline__ void nr_rows_load(const BackArgs& a, const BackLane& l, int call0, int gc, const float* row, float4 (&v)[8])
+{
+    nr_rows_each(a, l, call0, gc, [&](int k, int, int c, size_t rb, unsigned off)
+    {
+        v[k] = c < a.C ? *(const float4*)((row + rb) + off) : *(const float4*)(row + (size_t)(a.C - 1) * a.Nd + call0 * (BLK / 4) + 4 * (l.lane & 7));
+    });
+}
+
+__device__ __forceinline__ void nr_rows_to_lds(const BackArgs& a, const BackLane& l, int gc, const float4 (&v)[8], float* xs)
+{
+    nr_rows_each(a, l, 0, gc, [&](int k, int cc, int, size_t, unsigned)
+    {
+        float* r = xs + cc * FUSED_YPITCH + 4 * (l.lane & 7);
+        r[0] = v[k].x; r[1] = v[k].y; r[2] = v[k].z; r[3] = v[k].w;
+    });
+    wave_sync();                                         // every lane's row is whole
+}
+
+template <int PRE, int L, int W, bool AGC_ON>
+__device__ __forceinline__ void nr_head_body(const BackArgs& a, float* row, float* xs)
+{
+    const BackLane l(a);
+    constexpr int NDC = BLK / L;
+    const uhsdr_rx_plan* __restrict__ P = a.plan;
+    const uhsdr_agc_plan A = P->agc;
+    InStage<L> in;
+    LatticeStage<PRE, false> pre;
+    AgcStage<L, W> ag;
+    in.fetch(a, l, 0);
+    pre.load(l, P->pre_k, P->pre_v, a.s.pre);
+    ag.load(a, l, A);
+    ag.fetch(a, l, 0);
+    if (PRE > 0) { to_vgpr(pre.k); to_vgpr(pre.v); }
+    ag.agc_on = AGC_ON;
+    ag.dc = false; ag.dc_sel = false;                    // SSB / CW / DIGI: no DC removal
+    float* xl = xs + l.lane * FUSED_YPITCH;
+    for (int call0 = 0; call0 < l.calls; call0 += NR_GROUP)
+    {
+        const int gc = l.calls - call0 < NR_GROUP ? l.calls - call0 : NR_GROUP;
+        for (int q = 0; q < gc; ++q)
+        {
+            const int call = call0 + q;
+            float xin[NDC];
+            in.begin(a, l, call, xin);
+            ag.begin(a, l, call);
+#pragma unroll
+            for (int m = 0; m < NDC; ++m) xl[q * NDC + m] = ag.step(m, pre.step(xin[m], m), l, A);
+            ag.end(l);
+        }
+        nr_rows_store(a, l, call0, gc, xs, row);
+    }
+    pre.store(l, a.s.pre);
+    ag.store(a, l);
+}
+
+template <int PRE, int L, int W>
+__global__ void __launch_bounds__(BACK_CH) rx_nr_head(BackArgs a, float* row)
+{
+    static_assert(L == 4, "the firmware runs the stage on its 12 ksps paths only");
+    __shared__ float xs[BACK_CH * FUSED_YPITCH];
+    if (a.plan->agc.mode == 5) nr_head_body<PRE, L, W, false>(a, row, xs);
+    else nr_head_body<PRE, L, W, true>(a, row, xs);
+}
+
+// TAP: a_buffer[0] after biquad_1 replaces the lane's input sample in its LDS row, and the group's
+// rows leave for BackArgs::tap the way the head's leave for its row
+template <int AA, int L, int PH, bool CW, bool TAP>
+__device__ __forceinline__ void nr_tail_body(const BackArgs& a, const float* row, float* xs, float* ys)
+{
+    const BackLane l(a);
+    constexpr int NDC = BLK / L;
+    const uhsdr_rx_plan* __restrict__ P = a.plan;
+    AudioStage<L, PH, DM_NONE> au;
+    LatticeStage<AA, false> aa;
+    OutputStage ou;
+    float4 nx[8];
+    nr_rows_load(a, l, 0, l.calls < NR_GROUP ? l.calls : NR_GROUP, row, nx);
+    au.load(a, l);
+    aa.load(l, P->aa_k, P->aa_v, a.s.aa);
+    ou.load(a, l);
+    if (AA > 0) { to_vgpr(aa.k); to_vgpr(aa.v); }
+    to_vgpr(ou.b2);
+    ou.lo = to_vgpr(ou.lo);
+    to_vgpr(au.b1);
+    au.cw = CW;
+    float* xl = xs + l.lane * FUSED_YPITCH;
+    float* yl = ys + l.lane * FUSED_YPITCH;
+    for (int call0 = 0; call0 < l.calls; call0 += NR_GROUP)
+    {
+        const int gc = l.calls - call0 < NR_GROUP ? l.calls - call0 : NR_GROUP;
+        nr_rows_to_lds(a, l, gc, nx, xs);
+        // the next group's pieces are on their way while this one runs
+        const int left = l.calls - call0 - gc;
+        if (left > 0) nr_rows_load(a, l, call0 + gc, left < NR_GROUP ? left : NR_GROUP, row, nx);
+        for (int q = 0; q < gc; ++q)
+        {
+            const int call = call0 + q;
+#pragma unroll
+            for (int m = 0; m < NDC; ++m)
+            {
+                float u[L];
+                const float t = au.step_dec(xl[q * NDC + m]);
+                if constexpr (TAP) xl[q * NDC + m] = t;
+                au.interp(t, u);
+#pragma unroll
+                for (int j = 0; j < L; ++j) yl[m * L + j] = ou.step(aa.step(u[j], j));
+            }
+            fused_store_call(a, l, call, ys);
+            au.end(a, l, call);
+        }
+        if constexpr (TAP) nr_rows_store(a, l, call0, gc, xs, a.tap);
+        else wave_sync();                                // rows read before the next group writes
+    }
+    au.store(a, l);
+    aa.store(l, a.s.aa);
+    ou.store(a, l);
+}
+
+template <int AA, int L, int PH, bool TAP = false>
+__global__ void __launch_bounds__(BACK_CH) rx_nr_tail(BackArgs a, const float* row)
+{
+    static_assert(L == 4, "the firmware runs the stage on its 12 ksps paths only");
+    __shared__ float xs[BACK_CH * FUSED_YPITCH];
+    __shared__ float ys[BACK_CH * FUSED_YPITCH];
+    if (a.plan->cw_enabled) nr_tail_body<AA, L, PH, true, TAP>(a, row, xs, ys);
+    else nr_tail_body<AA, L, PH, false, TAP>(a, row, xs, ys);
+}
+
+// ------------------------------------------------------------------------------------
 // rx_chain: the whole call in one kernel for large batches (SSB / CW / DIGI, mono).  One wave
 // owns 64 channels: it runs rx_front's pass over them CPW channels at a time (64 / CPW passes,
 // the decimated output of each kept in LDS, [sample][channel] with pitch CHAIN_ADP), then
@@ -3345,8 +3531,15 @@ constexpr chain_fn chain_tap_of()
 #define FRONT_V(t1, t2, m, df, R) { t1, t2, m, df, rx_front<t1, t2, m, df, R, false>, R, rx_front<t1, t2, m, df, R, true>, 0 }
 #define FRONT_ST(t1, t2, m, df, R) { t1, t2, m, df, rx_front<t1, t2, m, df, R, false, true>, R, rx_front<t1, t2, m, df, R, true, true>, 1 }
 struct NotchVariant { int L, dm; back_fn fn; };
+// rx_nr_head / rx_nr_tail instances (uhsdr_rx_set_nr): the 12 ksps DM_NONE back ends of kBack;
+// tail_tap: the tail that also writes the digital-mode tap
+typedef void (*nr_head_fn)(BackArgs, float*);
+typedef void (*nr_tail_fn)(BackArgs, const float*);
+struct NrStageVariant { int pre, aa, L, ph, w; nr_head_fn head; nr_tail_fn tail, tail_tap; };
+#define NR_V(pre, aa, ph, w) { pre, aa, 4, ph, w, rx_nr_head<pre, 4, w>, rx_nr_tail<aa, 4, ph>, rx_nr_tail<aa, 4, ph, true> }
 #include <uhsdr_rx_variants.inc>
 #undef CHAIN_V
+#undef NR_V
 
 static int plan_dm(const uhsdr_rx_plan& p)
 {
@@ -3388,6 +3581,14 @@ static const ChainVariant* find_chain(const uhsdr_rx_plan& p, const BackVariant*
         if (v.t1 == t1 && v.t2 == t2 && v.m == p.decimation_rate && v.decim_first == p.use_decimated_iq &&
             v.pre == bv->pre && v.aa == bv->aa && v.L == bv->L && v.ph == bv->ph && v.w == bv->w)
             return &v;
+    return nullptr;
+}
+
+static const NrStageVariant* find_nr_stage(const BackVariant* bv)
+{
+    if (!bv || bv->dm != DM_NONE) return nullptr;
+    for (const NrStageVariant& v : kNrStage)
+        if (v.pre == bv->pre && v.aa == bv->aa && v.L == bv->L && v.ph == bv->ph && v.w == bv->w) return &v;
     return nullptr;
 }
 
@@ -3474,6 +3675,12 @@ struct uhsdr_rx_s
     uhsdr_rtty_handle rtty;  // RTTY text decoder (uhsdr_rx_set_rtty_text), null when off
     uhsdr_psk_handle psk;    // BPSK text decoder (uhsdr_rx_set_psk_text), null when off; never both
     float* text_tap;         // the decoder's input [C][Nd] when the user set no tap
+    // noise reduction / blanker between the AGC and biquad_1 (uhsdr_rx_set_nr): nsv = the head and tail
+    // kernels of the path's back end (null: none), nr = the 12 ksps stream (null: the stage is off),
+    // nr_in / nr_out = its [C][Nd] rows, a_buffer[0] as the firmware hands it over and takes it back
+    const NrStageVariant* nsv;
+    uhsdr_nr_handle nr;
+    float *nr_in, *nr_out;
     long long calls_done;
     long long front_launches; // oscillator ping-pong parity
     // pipelined mode (uhsdr_rx_set_pipelined): rx_back on a side stream, decimated hand-off
@@ -3867,6 +4074,12 @@ extern "C" uhsdr_status uhsdr_rx_reset(uhsdr_rx_handle h)
         const uhsdr_status cr = uhsdr_psk_reset(h->psk);
         if (cr != UHSDR_OK) return cr;
     }
+    if (h->nr)
+    {
+        // (the stage runs on the handle's stream only, and uhsdr_rx_set_stream moves it along)
+        const uhsdr_status cr = uhsdr_nr_reset(h->nr);
+        if (cr != UHSDR_OK) return cr;
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->dec_samples = 0;
     h->calls_done = 0;
@@ -3907,6 +4120,7 @@ extern "C" uhsdr_status uhsdr_rx_create(const uhsdr_rx_config* cfg, int32_t C, i
     h->bv = find_back(p);
     h->nv = find_notch(p);
     h->cv = find_chain(p, h->bv);
+    h->nsv = find_nr_stage(h->bv);
     if (!uhsdr_rx_mode_supported(&p) || !h->fv || !h->bv || (p.notch_enabled && !h->nv))
     {
         free(h);
@@ -4095,6 +4309,9 @@ static uhsdr_status launch_cw_text(uhsdr_rx_s* h, int cw0, hipStream_t st)
     return uhsdr_cwdec_launch(h->cwt, h->cw_signal ? h->cw_signal : h->cwt_signal, h->cw_blocks_last, h->N / BLK, first, cpb);
 }
 
+// rx_nr_tail stores the tap row in 16-byte pieces (the other tap kernels store single floats)
+static bool tap_aligned(const float* tap) { return ((uintptr_t)tap & 15) == 0; }
+
 // the digital-mode tap exists where the firmware runs its modems (audio_driver.c:2537-2557): a
 // 12 ksps path of the SSB / CW / DIGI back-end family, mono
 static uhsdr_status tap_supported(const uhsdr_rx_s* h, const char* what)
@@ -4117,6 +4334,11 @@ extern "C" uhsdr_status uhsdr_rx_set_digi_tap(uhsdr_rx_handle h, float* tap)
     {
         const uhsdr_status ts = tap_supported(h, "digi tap");
         if (ts != UHSDR_OK) return ts;
+    }
+    if (tap && h->nr && !tap_aligned(tap))
+    {
+        uhsdr_set_error("digi tap: the row must be 16-byte aligned while the noise reduction stage is on (uhsdr_rx_set_nr)");
+        return UHSDR_ARGUMENT_ERROR;
     }
     float* own = nullptr;
     if (!tap && (h->rtty || h->psk) && !h->text_tap)
@@ -4247,6 +4469,81 @@ static uhsdr_status launch_psk_text(uhsdr_rx_s* h, hipStream_t st)
     return uhsdr_psk_process(h->psk, tap_row(h), h->Nd, h->Nd);
 }
 
+// the noise reduction stage exists where the firmware runs it (audio_driver.c:2501) and where it is
+// built here: a 12 ksps path of the SSB / CW / DIGI back-end family, mono, no DC removal in the AGC,
+// the two-kernel schedules in serial mode, exact precision
+static uhsdr_status nr_supported(const uhsdr_rx_s* h, const char* what)
+{
+    const uhsdr_rx_plan& p = h->plan;
+    if (p.decimation_rate != 4 || plan_dm(p) != DM_NONE || p.stereo)
+    {
+        uhsdr_set_error("%s: needs a 12 ksps path of the SSB / CW / DIGI back end, mono (mode %d, decimation %d, stereo %d)",
+                        what, (int)p.dmod_mode, (int)p.decimation_rate, (int)p.stereo);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (p.agc.remove_dc) { uhsdr_set_error("%s: not with the AGC's DC removal on (the head kernel has none)", what); return UHSDR_ARGUMENT_ERROR; }
+    if (!h->nsv)
+    {
+        uhsdr_set_error("%s: no head / tail kernels for this back end (pre-filter %d, anti-alias %d stages, interpolator phase %d)",
+                        what, (int)p.pre_stages, (int)p.aa_stages, (int)p.interp_phase);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (h->schedule == UHSDR_SCHEDULE_CHAIN) { uhsdr_set_error("%s: not in UHSDR_SCHEDULE_CHAIN (one kernel per call)", what); return UHSDR_ARGUMENT_ERROR; }
+    if (h->pipelined) { uhsdr_set_error("%s: not in a pipelined mode (uhsdr_rx_set_pipelined 0 first)", what); return UHSDR_ARGUMENT_ERROR; }
+    if (h->precision == UHSDR_PRECISION_FMA) { uhsdr_set_error("%s: not with FMA precision", what); return UHSDR_ARGUMENT_ERROR; }
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_set_nr(uhsdr_rx_handle h, const uhsdr_nr_config* cfg)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    uhsdr_nr_handle nr = nullptr;
+    float *in = nullptr, *out = nullptr;
+    if (cfg)
+    {
+        // (argument errors before anything changes)
+        const uhsdr_status ss = nr_supported(h, "noise reduction stage");
+        if (ss != UHSDR_OK) return ss;
+        if (!tap_aligned(h->tap)) { uhsdr_set_error("noise reduction stage: the digital-mode tap row must be 16-byte aligned with the stage on"); return UHSDR_ARGUMENT_ERROR; }
+        // the stream decides the frames' rate itself (uhsdr_nr_process): uhsdr_nr_create judges the
+        // band at that rate
+        uhsdr_nr_config c = *cfg;
+        c.sample_rate = c.width_hz < 2701 ? 6000 : 12000;
+        const uhsdr_status st = uhsdr_nr_create(h->C, &c, h->stream, &nr);
+        if (st != UHSDR_OK) return st;
+        const size_t bytes = sizeof(float) * (size_t)h->C * h->Nd;
+        if (hipMalloc((void**)&in, bytes) != hipSuccess || hipMalloc((void**)&out, bytes) != hipSuccess)
+        {
+            uhsdr_set_error("noise reduction stage: device allocation failed");
+            if (in) (void)hipFree(in);
+            (void)uhsdr_nr_destroy(nr);
+            return UHSDR_DEVICE_ERROR;
+        }
+    }
+    HIPCHK(sync_all(h));
+    if (h->nr) (void)uhsdr_nr_destroy(h->nr);
+    if (h->nr_in) (void)hipFree(h->nr_in);
+    if (h->nr_out) (void)hipFree(h->nr_out);
+    h->nr = nr;
+    h->nr_in = in;
+    h->nr_out = out;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_rx_nr_state(uhsdr_rx_handle h, int32_t* first_time, int32_t* nn, float* power_ratio, int32_t* nb_last,
+                                          uint32_t* nb_total)
+{
+    if (!h || !h->nr) { uhsdr_set_error("the noise reduction stage is off (uhsdr_rx_set_nr)"); return UHSDR_ARGUMENT_ERROR; }
+    const uhsdr_status st = uhsdr_nr_state(h->nr, first_time, nn, power_ratio);
+    if (st != UHSDR_OK || (!nb_last && !nb_total)) return st;
+    const uhsdr_nb_handle nb = uhsdr_nr_blanker(h->nr);
+    if (nb) return uhsdr_nb_state(nb, nb_last, nb_total);
+    // no blanker: nothing repaired
+    if (nb_last) memset(nb_last, 0, sizeof(int32_t) * (size_t)h->C);
+    if (nb_total) memset(nb_total, 0, sizeof(uint32_t) * (size_t)h->C);
+    return UHSDR_OK;
+}
+
 extern "C" uhsdr_status uhsdr_rx_set_clip_output(uhsdr_rx_handle h, uint32_t* clip)
 {
     if (!h) return UHSDR_ARGUMENT_ERROR;
@@ -4293,6 +4590,8 @@ extern "C" uhsdr_status uhsdr_rx_set_stream(uhsdr_rx_handle h, void* stream)
     HIPCHK(hipEventRecord(h->ev_switch, h->stream));
     HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_switch, 0));
     h->stream = (hipStream_t)stream;
+    // the noise reduction stage's launches follow the handle's stream
+    if (h->nr) return uhsdr_nr_set_stream(h->nr, stream);
     return UHSDR_OK;
 }
 
@@ -4724,6 +5023,28 @@ static uhsdr_status launch_back(uhsdr_rx_s* h, const RxRoute& r, const BackArgs&
     return UHSDR_OK;
 }
 
+// the back end with the noise reduction stage (uhsdr_rx_set_nr; serial mode only, so everything runs
+// on the handle's stream): rx_notch where the plan has one, the head, the 12 ksps stream from one
+// row to the other, the tail
+static uhsdr_status launch_back_nr(uhsdr_rx_s* h, const BackArgs& bk)
+{
+    const dim3 grid((h->C + BACK_CH - 1) / BACK_CH), block(BACK_CH);
+    time_mark(h, K_BACK, 0);
+    if (h->nv)
+    {
+        hipLaunchKernelGGL(h->nv->fn, grid, block, 0, h->stream, bk);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(h->nsv->head, grid, block, 0, h->stream, bk, h->nr_in);
+    HIPCHK(hipGetLastError());
+    const uhsdr_status ns = uhsdr_nr_process(h->nr, h->nr_in, h->nr_out, h->Nd, h->Nd);
+    if (ns != UHSDR_OK) return ns;
+    hipLaunchKernelGGL(bk.tap ? h->nsv->tail_tap : h->nsv->tail, grid, block, 0, h->stream, bk, (const float*)h->nr_out);
+    HIPCHK(hipGetLastError());
+    time_mark(h, K_BACK, 1);
+    return UHSDR_OK;
+}
+
 static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audio, float* audio0, int32_t* dst)
 {
     if (!h || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
@@ -4752,7 +5073,8 @@ static uhsdr_status rx_process(uhsdr_rx_handle h, const int32_t* iq, float* audi
         if (r.dfl) handoff_args(h, r, bk);
         bool launch = true;
         if (r.pm) RXSTEP(pers_grant(h, r, bk, launch));
-        RXSTEP(launch_back(h, r, bk, launch));
+        if (h->nr) RXSTEP(launch_back_nr(h, bk));
+        else RXSTEP(launch_back(h, r, bk, launch));
         RXSTEP(launch_cw_text(h, cw0, back_stream(h)));
         RXSTEP(launch_rtty_text(h, back_stream(h)));
         RXSTEP(launch_psk_text(h, back_stream(h)));
@@ -4813,6 +5135,11 @@ extern "C" uhsdr_status uhsdr_rx_set_precision(uhsdr_rx_handle h, int32_t precis
                         (int)h->plan.filter_path, (int)h->plan.dmod_mode, h->plan.stereo ? " (stereo)" : "");
         return UHSDR_UNSUPPORTED;
     }
+    if (precision == UHSDR_PRECISION_FMA && h->nr)
+    {
+        uhsdr_set_error("FMA precision: the noise reduction stage is on (uhsdr_rx_set_nr), which is exact only");
+        return UHSDR_ARGUMENT_ERROR;
+    }
     h->precision = precision;
     return UHSDR_OK;
 }
@@ -4825,6 +5152,11 @@ extern "C" uhsdr_status uhsdr_rx_set_schedule(uhsdr_rx_handle h, int32_t schedul
     if (schedule < UHSDR_SCHEDULE_AUTO || schedule > UHSDR_SCHEDULE_CHAIN)
     {
         uhsdr_set_error("schedule %d: not a UHSDR_SCHEDULE_*", (int)schedule);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (schedule == UHSDR_SCHEDULE_CHAIN && h->nr)
+    {
+        uhsdr_set_error("schedule CHAIN: the noise reduction stage is on (uhsdr_rx_set_nr), which runs between two back-end kernels");
         return UHSDR_ARGUMENT_ERROR;
     }
     const int s = resolve_schedule(h, schedule);
@@ -4905,6 +5237,12 @@ extern "C" uhsdr_status uhsdr_rx_set_pipelined(uhsdr_rx_handle h, int32_t enable
     {
         uhsdr_set_error("pipelined mode %d: 0 (off), 1 (event hand-off), 2 (device hand-off) or 3 (persistent "
                         "back end)", (int)enable);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (enable && h->nr)
+    {
+        uhsdr_set_error("pipelined mode %d: the noise reduction stage is on (uhsdr_rx_set_nr), which runs in serial mode only",
+                        (int)enable);
         return UHSDR_ARGUMENT_ERROR;
     }
     if (enable == 3 && !h->run.pmem)
@@ -5034,6 +5372,9 @@ extern "C" uhsdr_status uhsdr_rx_destroy(uhsdr_rx_handle h)
     if (h->rtty) (void)uhsdr_rtty_destroy(h->rtty);
     if (h->psk) (void)uhsdr_psk_destroy(h->psk);
     if (h->text_tap) (void)hipFree(h->text_tap);
+    if (h->nr) (void)uhsdr_nr_destroy(h->nr);
+    if (h->nr_in) (void)hipFree(h->nr_in);
+    if (h->nr_out) (void)hipFree(h->nr_out);
     if (h->side)
     {
         (void)hipEventDestroy(h->ev_front);

@@ -68,3 +68,5 @@ static const ChainVariant kChain[] = {
     CHAIN_V(89, 4, 2, false, 8, 6, 2, 97),
 };
 
+// the back end split around the noise reduction stage (uhsdr_rx_set_nr): the 12 ksps SSB / CW / DIGI back ends
+static const NrStageVariant kNrStage[] = { NR_V(10, 6, 1, 49), NR_V(10, 0, 4, 49) };

@@ -215,6 +215,23 @@ class RxChain:
     def psk_text_outputs(self):
         return getattr(self, "_psk_text", None)
 
+    def set_nr(self, cfg: _abi.NrConfig | None = None) -> None:
+        """The firmware's noise reduction and blanker between the AGC and biquad_1 in every following
+        call (uhsdr_rx_set_nr): cfg as uhsdr_amd.nr.nr_config (nb_setting / nr_bypass: NR alone, NB then
+        NR, NB alone), a fresh stage each time; None turns it off.  12 ksps SSB / CW / DIGI paths, mono,
+        serial mode, exact precision."""
+        _abi.check(self.lib.uhsdr_rx_set_nr(self.handle, C.byref(cfg) if cfg is not None else None), "uhsdr_rx_set_nr")
+        self._nr_cfg = cfg
+
+    def nr_state(self):
+        """(first_time int32 [C], NN int32 [C], power_ratio float32 [C], nb_last int32 [C], nb_total
+        uint32 [C]) of the stage after everything enqueued; the blanker's two are zero while it is off."""
+        ft, nn, last = (np.empty(self.channels, np.int32) for _ in range(3))
+        pr, tot = np.empty(self.channels, np.float32), np.empty(self.channels, np.uint32)
+        _abi.check(self.lib.uhsdr_rx_nr_state(self.handle, *(x.ctypes.data_as(C.c_void_p) for x in (ft, nn, pr, last, tot))),
+                   "uhsdr_rx_nr_state")
+        return ft, nn, pr, last, tot
+
     @property
     def cw_blocks_max(self) -> int:
         return self.lib.uhsdr_rx_cw_blocks_max(self.handle)
