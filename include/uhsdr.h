@@ -1197,6 +1197,107 @@ uhsdr_status uhsdr_rx_set_nr(uhsdr_rx_handle h, const uhsdr_nr_config* cfg);
 uhsdr_status uhsdr_rx_nr_state(uhsdr_rx_handle h, int32_t* first_time, int32_t* nn, float* power_ratio, int32_t* nb_last,
                                uint32_t* nb_total);
 
+/* ---- Signal meter: display frames of sd.FFT_MagData in, dBm, dBm/Hz, S-units and SNAP carrier out ----
+ * What the firmware's front panel shows of a channel's strength and tuning, one instance per channel,
+ * once per completed display frame and in this order: UiSpectrum_CalculateDBm with
+ * UiSpectrum_CalculateSnap (drivers/ui/lcd/ui_spectrum.c:1876-2123), the attack / decay averagers of
+ * RadioManagement_HandleIqGainAndSMeter and the S-unit search of UiDriver_HandleSMeter
+ * (drivers/ui/ui_driver.c:4629-4696).  The firmware runs the three on timers of its own main loop;
+ * here every frame gets exactly one of each.  Exact to the reference: the same bits in all six outputs.
+ *   fft_len            256 or 512: the display's bins, sd.spec_len (the firmware's fft_iq_len 512 / 1024),
+ *                      as in uhsdr_spectrum_config.  1024 is UHSDR_ARGUMENT_ERROR: the firmware has
+ *                      no such frame, so its dBm constant is undefined there
+ *   magnify            sd.magnify, 0 .. 5;  iq_freq_mode  ts.iq_freq_mode (both as uhsdr_spectrum_config)
+ *   dmod_mode, filter_path, sam_sideband, cw_lsb, digi_lsb, cw_sidetone_freq
+ *                      as in uhsdr_rx_config; the path gives FilterInfo[].width and the path's offset
+ *   digital_mode       ts.digital_mode as UHSDR_DIGITAL_MODE_*; only BPSK matters (is_demod_psk)
+ *   dbm_constant       ts.dbm_constant, -100 .. 100, default 0
+ *   attack_alpha, decay_alpha   sm.config.alphaSplit, 1 .. 100, defaults 50 / 5 (audio_driver.h:293-296)
+ *   snap_enable        cw_decoder_config.snap_enable, default 1 (cw_decoder.c:63)
+ *   tune_old           df.tune_old in Hz, one value for the handle
+ * A configuration whose passband bins do not satisfy 0 <= Lbin <= Ubin <= fft_len - 1 after the
+ * firmware's two clamps (it would index outside sd.FFT_Samples) is UHSDR_ARGUMENT_ERROR.
+ * SNAP runs in CW (on the frames whose cw_signal byte is non-zero), AM, SAM and DIGI with BPSK while
+ * snap_enable is set; on every other frame snap_carrier_freq keeps its last value (0 after a reset).
+ * process_mag: mag = f32 [C][frames][fft_len], frames of FFT_MagData in natural bin order as
+ * uhsdr_spectrum_process writes them, device memory (host memory for process_mag_host), stream-ordered;
+ * io (null: no output but the state) holds optional rows, each [C][frames], null: not wanted.
+ * state: the last outputs per channel into host arrays of num_channels (null: not wanted) after
+ * everything enqueued.  reset: averages and outputs 0, freq_old 1e7 as the firmware starts.
+ * Reference oddities kept: a passband without a sample above zero "finds" bin 1; a NaN never wins
+ * the search; NaN and infinities pass through the sum and the interpolation as they come; a passband
+ * of one bin (Lbin == Ubin, as the clamp at 0 gives for CW on the lower sideband with the 300 Hz filter
+ * centred on 900 Hz at magnify 5) has a dBm/Hz term of 10 log10(0), finite with Math_log10f_fast; dbm above the
+ * table's end is S-count 33.  Defined here, not kept: with the maximum in the last bin the firmware
+ * reads one float behind sd.FFT_Samples, here that neighbour is 0; (ulong)help_freq of a NaN, a
+ * negative value or one of 2^32 and above is undefined in C, here it is 0.
+ * Not built: the codec-gain servo (RadioManagement_HandleRxIQSignalCodecGain), the sc.snap tune
+ * request and its counter, all drawing, a per-channel tune_old, the meter on the 1024-point
+ * spectrum, inside uhsdr_rx_* or uhsdr_i2s_*, the TX power / SWR meters, any FMA mode. */
+enum { UHSDR_DIGITAL_MODE_NONE = 0, UHSDR_DIGITAL_MODE_RTTY = 1, UHSDR_DIGITAL_MODE_BPSK = 2 };
+typedef struct uhsdr_meter_config
+{
+    int32_t fft_len, magnify, iq_freq_mode;
+    int32_t dmod_mode, filter_path, sam_sideband, cw_lsb, digi_lsb, digital_mode, cw_sidetone_freq;
+    int32_t dbm_constant, attack_alpha, decay_alpha, snap_enable;
+    uint32_t tune_old;
+    int32_t reserved[9];
+} uhsdr_meter_config;
+/* what UiSpectrum_CalculateDBm computes before its loops (:2003-2082), and the rest a frame needs */
+typedef struct uhsdr_meter_plan
+{
+    int32_t fft_len, magnify, iq_freq_mode;
+    int32_t bin_offset, posbin;
+    int32_t lbin, ubin;                     /* (int)Lbin, (int)Ubin after the clamps */
+    int32_t snap;                           /* 0 never, 1 every frame, 2 CW: the frames with cw_signal */
+    uint32_t tune_old;
+    float   bin_bw, width, offset, bw_lower, bw_upper;
+    float   cons;                           /* dbm_constant - 225 - (3 at fft_iq_len 1024) */
+    float   dbmhz_term;                     /* 10 * Math_log10f_fast((Ubin - Lbin) * bin_BW) */
+    float   snap_offset;                    /* CW: -+ cw_sidetone_freq, BPSK: +- PSK_OFFSET, else 0 */
+    float   attack_alpha, decay_alpha;      /* the config's times 0.01f */
+    float   s_cal_dbm[33];                  /* S_Meter_Cal_dbm */
+    int32_t reserved[5];
+} uhsdr_meter_plan;
+typedef struct uhsdr_meter_io
+{
+    float*    dbm_cur;                      /* sm.dbm_cur */
+    float*    dbmhz_cur;                    /* sm.dbmhz_cur */
+    float*    dbm;                          /* sm.dbm */
+    float*    dbmhz;                        /* sm.dbmhz */
+    int32_t*  s_count;                      /* sm.s_count, 1 .. 33 */
+    uint32_t* snap_carrier_freq;            /* ads.snap_carrier_freq */
+    const uint8_t* cw_signal;               /* input: ads.CW_signal at each frame; null: 0, a decoder that never saw a pulse */
+} uhsdr_meter_io;
+typedef struct uhsdr_meter_s* uhsdr_meter_handle;
+
+void         uhsdr_meter_config_default(uhsdr_meter_config* cfg);
+uhsdr_status uhsdr_meter_plan_build(const uhsdr_meter_config* cfg, uhsdr_meter_plan* plan);
+uhsdr_status uhsdr_meter_create(int32_t num_channels, const uhsdr_meter_config* cfg, void* stream, uhsdr_meter_handle* out);
+/* the same meter with its state in host memory, for the _host call (no device call) */
+uhsdr_status uhsdr_meter_create_host(int32_t num_channels, const uhsdr_meter_config* cfg, uhsdr_meter_handle* out);
+uhsdr_status uhsdr_meter_reset(uhsdr_meter_handle h);
+uhsdr_status uhsdr_meter_set_stream(uhsdr_meter_handle h, void* stream);
+uhsdr_status uhsdr_meter_process_mag(uhsdr_meter_handle h, const float* mag, int32_t frames, const uhsdr_meter_io* io);
+uhsdr_status uhsdr_meter_process_mag_host(uhsdr_meter_handle h, const float* mag, int32_t frames, const uhsdr_meter_io* io);
+uhsdr_status uhsdr_meter_state(uhsdr_meter_handle h, float* dbm_cur, float* dbmhz_cur, float* dbm, float* dbmhz, int32_t* s_count,
+                               uint32_t* snap_carrier_freq);
+uhsdr_status uhsdr_meter_synchronize(uhsdr_meter_handle h);
+uhsdr_status uhsdr_meter_destroy(uhsdr_meter_handle h);
+int32_t      uhsdr_sizeof_meter_config(void);
+int32_t      uhsdr_sizeof_meter_plan(void);
+/* The meter inside the spectrum: with a device meter attached, every uhsdr_spectrum_process runs the
+   meter's frame on the magnitudes of each display frame it completes, where they lie staged in LDS,
+   and writes io's rows ([C][F], F as for mag / avg; io is copied, null: the state only).  mag and avg
+   may then both be null: such a call writes no spectrum at all.  A call that completes no frame
+   writes nothing.  The meter's state moves exactly as under uhsdr_meter_process_mag on the same
+   frames.  meter null detaches: calls then enqueue what they enqueued before.  UHSDR_ARGUMENT_ERROR
+   unless fft_len, magnify and iq_freq_mode of the two agree, the meter is a device handle and both
+   are on one stream; the caller keeps the meter alive and on that stream while it is attached: after a
+   uhsdr_meter_set_stream to another one, uhsdr_spectrum_process is UHSDR_ARGUMENT_ERROR until the
+   meter is detached or moved back. */
+uhsdr_status uhsdr_spectrum_set_meter(uhsdr_spectrum_handle h, uhsdr_meter_handle meter, const uhsdr_meter_io* io);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-# Host ASan / UBSan build and run of the seven module drivers (tools/*/*_sanitize.c), included by the
+# Host ASan / UBSan build and run of the eight module drivers (tools/*/*_sanitize.c), included by the
 # top-level Makefile:
 #
 #   make sanitize          (objects, programs, their input files and logs under tests/build/sanitize/)
@@ -18,7 +18,8 @@ PYTHON       ?= python3
 
 # program: its directory under tools/, its dump script, the module sources it links (uhsdr_<m>.hip).
 # cwgen takes the text queue's put from digimod, nr's stream can hold a noise blanker; nb_sanitize
-# is plain C over uhsdr_nb.h and links nothing else.
+# and meter_sanitize are plain C over uhsdr_nb.h and uhsdr_meter.h and link nothing else (the meter's
+# dump script writes each case's plan, built through libuhsdr_amd.so).
 SAN_cwdec   := cwtext  dump_states.py  cwdec
 SAN_rtty    := rtty    dump_streams.py rtty
 SAN_psk     := psk     dump_streams.py psk
@@ -26,7 +27,8 @@ SAN_digimod := digimod dump_cases.py   digimod
 SAN_cwgen   := cwgen   dump_cases.py   cwgen digimod
 SAN_nr      := nr      dump_cases.py   nr nb
 SAN_nb      := nb      dump_cases.py
-SAN_PROGS   := cwdec rtty psk digimod cwgen nr nb
+SAN_meter   := meter   dump_cases.py
+SAN_PROGS   := cwdec rtty psk digimod cwgen nr nb meter
 SAN_HOST    := $(SAN)/uhsdr_setup.o $(SAN)/uhsdr_filter_tables.o
 
 sanitize: $(LIB) $(SAN_PROGS:%=$(SAN)/%.log)

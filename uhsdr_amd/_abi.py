@@ -178,6 +178,28 @@ class NbConfig(C.Structure):
     _fields_ = [("nb_setting", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+DIGITAL_MODE_NONE, DIGITAL_MODE_RTTY, DIGITAL_MODE_BPSK = range(3)   # uhsdr_meter_config.digital_mode
+
+
+class MeterConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "fft_len", "magnify", "iq_freq_mode", "dmod_mode", "filter_path", "sam_sideband", "cw_lsb", "digi_lsb",
+        "digital_mode", "cw_sidetone_freq", "dbm_constant", "attack_alpha", "decay_alpha", "snap_enable")] + [
+        ("tune_old", C.c_uint32), ("reserved", C.c_int32 * 9)]
+
+
+class MeterPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fft_len", "magnify", "iq_freq_mode", "bin_offset", "posbin", "lbin", "ubin", "snap")] + [
+        ("tune_old", C.c_uint32)] + [(n, C.c_float) for n in (
+            "bin_bw", "width", "offset", "bw_lower", "bw_upper", "cons", "dbmhz_term", "snap_offset", "attack_alpha",
+            "decay_alpha")] + [("s_cal_dbm", C.c_float * 33), ("reserved", C.c_int32 * 5)]
+
+
+class MeterIo(C.Structure):
+    """uhsdr_meter_io: optional rows [C][frames], 0: not wanted"""
+    _fields_ = [(n, C.c_void_p) for n in ("dbm_cur", "dbmhz_cur", "dbm", "dbmhz", "s_count", "snap_carrier_freq", "cw_signal")]
+
+
 # every exported entry point of include/uhsdr.h: name -> (restype, argtypes)
 SIGNATURES = {
     "uhsdr_rx_config_default": (None, [C.POINTER(RxConfig)]),
@@ -348,6 +370,20 @@ SIGNATURES = {
     "uhsdr_nb_destroy": (C.c_int, [C.c_void_p]),
     "uhsdr_rx_set_nr": (C.c_int, [C.c_void_p, C.POINTER(NrConfig)]),
     "uhsdr_rx_nr_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhsdr_meter_config_default": (None, [C.POINTER(MeterConfig)]),
+    "uhsdr_meter_plan_build": (C.c_int, [C.POINTER(MeterConfig), C.POINTER(MeterPlan)]),
+    "uhsdr_meter_create": (C.c_int, [C.c_int32, C.POINTER(MeterConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_meter_create_host": (C.c_int, [C.c_int32, C.POINTER(MeterConfig), C.POINTER(C.c_void_p)]),
+    "uhsdr_meter_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_meter_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_meter_process_mag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MeterIo)]),
+    "uhsdr_meter_process_mag_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MeterIo)]),
+    "uhsdr_meter_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
+    "uhsdr_meter_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_meter_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_sizeof_meter_config": (C.c_int32, []),
+    "uhsdr_sizeof_meter_plan": (C.c_int32, []),
+    "uhsdr_spectrum_set_meter": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MeterIo)]),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -409,6 +445,8 @@ def load(path: str | None = None) -> C.CDLL:
     if (lib.uhsdr_sizeof_spectrum_config() != C.sizeof(SpectrumConfig)
             or lib.uhsdr_sizeof_spectrum_plan() != C.sizeof(SpectrumPlan)):
         raise RuntimeError("ctypes layout of uhsdr_spectrum_config / _plan does not match include/uhsdr.h")
+    if not variant and (lib.uhsdr_sizeof_meter_config() != C.sizeof(MeterConfig) or lib.uhsdr_sizeof_meter_plan() != C.sizeof(MeterPlan)):
+        raise RuntimeError("ctypes layout of uhsdr_meter_config / _plan does not match include/uhsdr.h")
     if path is None:
         _lib = lib
     return lib

@@ -42,6 +42,7 @@
 #include <chrono>
 #include "uhsdr_internal.h"
 #include "uhsdr_libm.h"
+#include "uhsdr_log10f_fast.h"
 #include "uhsdr_dsp.h"
 
 // channels per back-end workgroup (lane == channel): the unit of the device hand-off's arrival counters
@@ -762,22 +763,6 @@ __device__ __forceinline__ float beep_tone(const BackArgs& a, int n)
     const uhsdr_rx_plan* __restrict__ P = a.plan;
     const uint32_t acc = a.beep_acc + (uint32_t)(n - a.beep_n0) * P->beep_step;
     return (float)P->dds_table[(acc >> 22) % 1024] * P->beep_scale;
-}
-
-// Math_log10f_fast, misc/uhsdr_math.c:26-39
-__device__ __forceinline__ float log10f_fast(float X)
-{
-    int E;
-    const float F = frexpf(fabsf(X), &E);
-    float Y = 1.23149591368684f;
-    Y *= F;
-    Y += -4.11852516267426f;
-    Y *= F;
-    Y += 6.02197014179219f;
-    Y *= F;
-    Y += -3.13396450166353f;
-    Y += (float)E;
-    return (Y * 0.3010299956639812f);
 }
 
 // float -> int32 as the x86 reference converts (cvttss2si: out of range / NaN -> INT32_MIN),

@@ -866,3 +866,157 @@ uhsdr_status uhsdr_spectrum_plan_build(const uhsdr_spectrum_config* cfg, uhsdr_s
 
 int32_t uhsdr_sizeof_spectrum_config(void) { return (int32_t)sizeof(uhsdr_spectrum_config); }
 int32_t uhsdr_sizeof_spectrum_plan(void) { return (int32_t)sizeof(uhsdr_spectrum_plan); }
+
+/* ---- signal meter: what UiSpectrum_CalculateDBm computes before its loops (ui_spectrum.c:2003-2082),
+   SNAP's mode test and offset (:2094, :1939-1955), the averagers' factors (ui_driver.c:4642-4645) ---- */
+#include "uhsdr_meter.h"
+#include "uhsdr_meter_tables.h"
+
+#define PSK_OFFSET 500                      /* drivers/audio/psk.h:17 */
+#define PSK_SNAP_RANGE 100                  /* :18 */
+
+void uhsdr_meter_config_default(uhsdr_meter_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->fft_len = 256;
+    cfg->iq_freq_mode = UHSDR_IQ_CONV_M12KHZ;    /* as uhsdr_rx_config_default */
+    cfg->dmod_mode = UHSDR_DEMOD_USB;
+    cfg->filter_path = 48;
+    cfg->sam_sideband = UHSDR_SAM_SIDEBAND_BOTH;
+    cfg->cw_sidetone_freq = 750;
+    cfg->attack_alpha = 50;                      /* SMETER_ALPHA_ATTACK_DEFAULT, audio_driver.h:293 */
+    cfg->decay_alpha = 5;                        /* SMETER_ALPHA_DECAY_DEFAULT, :294 */
+    cfg->snap_enable = 1;                        /* cw_decoder.c:63 */
+}
+
+/* RadioManagement_UsesBothSidebands with USE_TWO_CHANNEL_AUDIO (radio_management.c:1643-1663) */
+static int meter_both_sidebands(const uhsdr_meter_config* c)
+{
+    return c->dmod_mode == UHSDR_DEMOD_AM || (c->dmod_mode == UHSDR_DEMOD_SAM && c->sam_sideband == UHSDR_SAM_SIDEBAND_BOTH)
+        || c->dmod_mode == UHSDR_DEMOD_FM || c->dmod_mode == UHSDR_DEMOD_SSBSTEREO || c->dmod_mode == UHSDR_DEMOD_IQ
+        || (c->dmod_mode == UHSDR_DEMOD_SAM && c->sam_sideband == UHSDR_SAM_SIDEBAND_STEREO);
+}
+
+/* RadioManagement_LSBActive (:1665-1690) */
+static int meter_lsb_active(const uhsdr_meter_config* c)
+{
+    switch (c->dmod_mode)
+    {
+    case UHSDR_DEMOD_SAM: return c->sam_sideband == UHSDR_SAM_SIDEBAND_LSB;
+    case UHSDR_DEMOD_LSB: return 1;
+    case UHSDR_DEMOD_CW: return c->cw_lsb != 0;
+    case UHSDR_DEMOD_DIGI: return c->digi_lsb != 0;
+    default: return 0;
+    }
+}
+
+uhsdr_status uhsdr_meter_plan_build(const uhsdr_meter_config* cfg, uhsdr_meter_plan* p)
+{
+    if (!cfg || !p) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->fft_len != 256 && cfg->fft_len != 512)
+    {
+        uhsdr_set_error("meter: fft_len %d: need 256 or 512 (the firmware has no frame of 1024 bins, so no dBm constant for it)", cfg->fft_len);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (cfg->magnify < 0 || cfg->magnify > 5)
+    { uhsdr_set_error("meter: magnify %d outside 0..5 (MAGNIFY_MIN..MAGNIFY_MAX)", cfg->magnify); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->iq_freq_mode < UHSDR_IQ_CONV_OFF || cfg->iq_freq_mode > UHSDR_IQ_CONV_M12KHZ)
+    { uhsdr_set_error("meter: iq_freq_mode %d unknown", cfg->iq_freq_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->dmod_mode < UHSDR_DEMOD_USB || cfg->dmod_mode > UHSDR_DEMOD_IQ)
+    { uhsdr_set_error("meter: dmod_mode %d unknown", cfg->dmod_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->filter_path <= 0 || cfg->filter_path >= UHSDR_FILTER_PATH_NUM)
+    { uhsdr_set_error("meter: filter_path %d out of range 1..%d", cfg->filter_path, UHSDR_FILTER_PATH_NUM - 1); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->sam_sideband < UHSDR_SAM_SIDEBAND_BOTH || cfg->sam_sideband > UHSDR_SAM_SIDEBAND_STEREO)
+    { uhsdr_set_error("meter: sam_sideband %d unknown", cfg->sam_sideband); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->dbm_constant < -100 || cfg->dbm_constant > 100)
+    { uhsdr_set_error("meter: dbm_constant %d outside -100..100", cfg->dbm_constant); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->attack_alpha < 1 || cfg->attack_alpha > 100 || cfg->decay_alpha < 1 || cfg->decay_alpha > 100)
+    { uhsdr_set_error("meter: attack_alpha %d / decay_alpha %d outside 1..100", cfg->attack_alpha, cfg->decay_alpha); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->cw_sidetone_freq < 0 || cfg->cw_sidetone_freq > 65535)
+    { uhsdr_set_error("meter: cw_sidetone_freq %d out of range", cfg->cw_sidetone_freq); return UHSDR_ARGUMENT_ERROR; }
+    memset(p, 0, sizeof *p);
+    p->fft_len = cfg->fft_len;
+    p->magnify = cfg->magnify;
+    p->iq_freq_mode = cfg->iq_freq_mode;
+    p->tune_old = cfg->tune_old;
+
+    const int buff_len_int = 2 * cfg->fft_len;          /* sd.fft_iq_len */
+    const float buff_len = buff_len_int;
+    const float cons = cfg->dbm_constant - 225 - (buff_len_int == 1024 ? 3 : 0);
+    const float bin_BW = (float)IQ_SAMPLE_RATE * 2.0 / (buff_len * (1 << cfg->magnify));
+
+    float width = uhsdr_meter_path_width[cfg->filter_path];
+    float offset = uhsdr_meter_path_offset[cfg->filter_path];
+    if (offset == 0) offset = width / 2;
+    const float lf_freq = offset - width / 2;
+    const float uf_freq = offset + width / 2;
+
+    const int psk = cfg->dmod_mode == UHSDR_DEMOD_DIGI && cfg->digital_mode == UHSDR_DIGITAL_MODE_BPSK;   /* is_demod_psk */
+    float bw_LOWER = 0.0, bw_UPPER = 0.0;
+    if (meter_both_sidebands(cfg))
+    {
+        bw_UPPER = uf_freq;
+        bw_LOWER = -uf_freq;
+    }
+    else if (meter_lsb_active(cfg))
+    {
+        bw_UPPER = -lf_freq;
+        bw_LOWER = -uf_freq;
+    }
+    else if (psk)
+    {
+        bw_LOWER = PSK_OFFSET - PSK_SNAP_RANGE;
+        bw_UPPER = PSK_OFFSET + PSK_SNAP_RANGE;
+    }
+    else
+    {
+        bw_UPPER = uf_freq;
+        bw_LOWER = lf_freq;
+    }
+
+    int32_t translate = 0, kind = 0, up = 0;            /* AudioDriver_GetTranslateFreq */
+    float oc = 0, os = 0;
+    shift_plan(cfg->iq_freq_mode, &translate, &kind, &up, &oc, &os);
+    const int32_t bin_offset = cfg->magnify != 0 ? 0 : (-(buff_len_int * translate) / (2 * IQ_SAMPLE_RATE));
+    const int32_t posbin = buff_len_int / 4 + bin_offset;
+
+    float Lbin = (float)posbin + roundf(bw_LOWER / bin_BW);
+    float Ubin = (float)posbin + roundf(bw_UPPER / bin_BW);
+    if (cfg->dmod_mode == UHSDR_DEMOD_SAM && cfg->sam_sideband == UHSDR_SAM_SIDEBAND_USB) Lbin = Lbin - 1.0;
+    if (Lbin < 0) Lbin = 0;
+    if (Ubin > (cfg->fft_len - 1)) Ubin = cfg->fft_len - 1;
+    /* the firmware clamps no further; what is left outside would index outside sd.FFT_Samples */
+    if (!(Lbin <= Ubin) || Ubin < 0 || Lbin > cfg->fft_len - 1)
+    {
+        uhsdr_set_error("meter: passband bins [%g, %g] of filter_path %d at magnify %d do not lie in 0..%d in order", (double)Lbin,
+                        (double)Ubin, cfg->filter_path, cfg->magnify, cfg->fft_len - 1);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    p->bin_offset = bin_offset;
+    p->posbin = posbin;
+    p->lbin = (int)Lbin;
+    p->ubin = (int)Ubin;
+    p->bin_bw = bin_BW;
+    p->width = width;
+    p->offset = offset;
+    p->bw_lower = bw_LOWER;
+    p->bw_upper = bw_UPPER;
+    p->cons = cons;
+    p->dbmhz_term = 10 * log10f_fast((float)(((int)Ubin - (int)Lbin) * bin_BW));
+
+    const int cw = cfg->dmod_mode == UHSDR_DEMOD_CW;
+    const int carrier = cfg->dmod_mode == UHSDR_DEMOD_AM || cfg->dmod_mode == UHSDR_DEMOD_SAM || psk;
+    p->snap = !cfg->snap_enable ? METER_SNAP_NEVER : carrier ? METER_SNAP_ALWAYS : cw ? METER_SNAP_CW : METER_SNAP_NEVER;
+    if (cw) p->snap_offset = (cfg->cw_lsb ? 1.0 : -1.0) * (float)cfg->cw_sidetone_freq;
+    if (psk) p->snap_offset = cfg->digi_lsb ? (float)PSK_OFFSET : -(float)PSK_OFFSET;
+
+    const float alpha_scale_inv = 0.01;
+    p->attack_alpha = cfg->attack_alpha * alpha_scale_inv;
+    p->decay_alpha = cfg->decay_alpha * alpha_scale_inv;
+    copy_bits(p->s_cal_dbm, uhsdr_meter_s_cal_dbm, METER_S_SIZE);
+    return UHSDR_OK;
+}
+
+int32_t uhsdr_sizeof_meter_config(void) { return (int32_t)sizeof(uhsdr_meter_config); }
+int32_t uhsdr_sizeof_meter_plan(void) { return (int32_t)sizeof(uhsdr_meter_plan); }

@@ -25,6 +25,7 @@
 #include "uhsdr_internal.h"
 #include "uhsdr_dsp.h"
 #include "uhsdr_cfft.h"
+#include "uhsdr_meter_host.h"
 
 namespace {
 
@@ -183,11 +184,12 @@ __device__ __forceinline__ SpecParams spec_params(const uhsdr_spectrum_plan* __r
 // One display frame from the produced positions z[k] = x[lane + 64k]: arm_cfft_f32's first
 // stages in registers, the middle radix-8 stage through LDS, the last stage into registers,
 // the bit reversal as the output bin of each butterfly result, then magnitude and average
-// (ui_spectrum.c:1405, 1432-1446).
-template <int L>
+// (ui_spectrum.c:1405, 1432-1446).  METER: then the signal meter's frame (uhsdr_meter.h) on the
+// magnitudes where they lie staged, with the channel's meter state `ms` in registers.
+template <int L, bool METER = false>
 __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], float2* X, const float* __restrict__ tw,
                                                float (&av)[SpecGeom<L>::R3][8], float f, const SpecArgs& a, int c,
-                                               int frame, int lane)
+                                               int frame, int lane, const MeterArgs* m = nullptr, meter_state* ms = nullptr)
 {
     using G = SpecGeom<L>;
     constexpr int NBF = G::NBF, R3 = G::R3;
@@ -231,6 +233,12 @@ __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], floa
         if (mo) *(float4*)(mo + i) = *(const float4*)(O + i);
         if (ao) *(float4*)(ao + i) = *(const float4*)(O + L + i);
     }
+    if constexpr (METER)
+    {
+        const size_t at = (size_t)c * a.F + frame;
+        meter_wave_frame(m->plan, *ms, O, m->io.cw_signal ? m->io.cw_signal[at] : 0, lane);
+        if (lane == 0) meter_write(m->io, *ms, at);
+    }
     wave_sync();                                 // staged outputs read before the next frame lands
 }
 
@@ -262,6 +270,7 @@ __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_accumulate(SpecArgs 
 }
 
 // Calls that complete frames: every segment ends a frame; the first may start from the carry.
+// spectrum_frames_meter below is this walk again with the signal meter in it: a change here belongs there too.
 template <int L, bool AUTO, bool ZM>
 __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames(SpecArgs a)
 {
@@ -335,6 +344,89 @@ __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames(SpecArgs a)
             for (int k = 0; k < 8; ++k) a.avg_state[row + 8 * q + k] = av[r][k];
     }
     if (AUTO && lane == 0) { a.teta[c] = o1; a.teta[C + c] = o2; a.teta[2 * C + c] = o3; }
+}
+
+// spectrum_frames with a signal meter attached (uhsdr_spectrum_set_meter): the same walk over the
+// call's frames, with the channel's meter state in registers beside the averages and the meter's
+// frame run on every completed frame's staged magnitudes (spectrum_frame<L, true>).  A kernel of its
+// own, with its own argument, and not a parameter of spectrum_frames: the instances without a meter
+// keep the code they had.
+template <int L, bool AUTO, bool ZM>
+__global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames_meter(SpecArgs a, MeterArgs m)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    using G = SpecGeom<L>;
+    constexpr int K = G::K, NBF = G::NBF, R3 = G::R3;
+    const uhsdr_spectrum_plan* __restrict__ P = a.plan;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * SPEC_WAVES + w;
+    if (c >= a.C) return;                        // whole wave; no workgroup barrier below
+    float* S = smem + w * a.lds_pitch;           // auto-I/Q products, then the frame
+    float2* X = (float2*)S;
+    float* T = S + G::REGION;                    // used only with auto I/Q correction
+    const float* __restrict__ tw = P->twiddle;
+    const SpecParams sp = spec_params<L>(P);
+    const float f = P->filt_factor;
+    const int C = a.C, N = a.N;
+    const size_t row = (size_t)c * L;
+
+    // the final-stage outputs this lane owns: positions 8q + k, q = lane + 64r; their running
+    // averages stay in registers (state kept in position order, bins via plan->iperm)
+    float av[R3][8];
+#pragma unroll
+    for (int r = 0; r < R3; ++r)
+    {
+        const int q = lane + 64 * r;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) av[r][k] = q < NBF ? a.avg_state[row + 8 * q + k] : 0.0f;
+    }
+    float o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+    if (AUTO) { o1 = a.teta[c]; o2 = a.teta[C + c]; o3 = a.teta[2 * C + c]; }
+    meter_state ms;
+    meter_state_load(ms, m.state, C, c);
+    using SrcT = typename std::conditional<ZM, float2, int2>::type;
+    const SrcT* __restrict__ src;
+    if constexpr (ZM) src = a.zq + (size_t)c * a.ld;
+    else src = a.iq + (size_t)c * a.ld;
+
+    int n0 = 0, frame = 0;
+    if (a.fill0)
+    {
+        // ---- the frame begun in earlier calls ----
+        const float2* __restrict__ carry = (const float2*)a.carry + (size_t)c * L;
+        float2 z[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+        {
+            const int p = lane + 64 * k;
+            z[k] = carry[p < a.fill0 ? p : 0];
+        }
+        produce<L, true, AUTO && !ZM, ZM>(z, src, a.fill0, L, sp, S, T, o1, o2, o3, lane);
+        spectrum_frame<L, true>(z, X, tw, av, f, a, c, frame, lane, &m, &ms);
+        n0 = L - a.fill0;
+        ++frame;
+    }
+    for (; n0 < N; n0 += L, ++frame)
+    {
+        // per-frame reloads (L1-resident) instead of loop-invariant registers: keeps the window
+        // and the twiddles from being hoisted out of the frame loop into VGPRs
+        SpecParams spf = sp;
+        const float* __restrict__ twf = tw;
+        asm volatile("" : "+s"(spf.win), "+s"(twf));
+        float2 z[K];
+        produce<L, false, AUTO && !ZM, ZM>(z, src + n0, 0, L, spf, S, T, o1, o2, o3, lane);
+        spectrum_frame<L, true>(z, X, twf, av, f, a, c, frame, lane, &m, &ms);
+    }
+#pragma unroll
+    for (int r = 0; r < R3; ++r)
+    {
+        const int q = lane + 64 * r;
+        if (q < NBF)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a.avg_state[row + 8 * q + k] = av[r][k];
+    }
+    if (AUTO && lane == 0) { a.teta[c] = o1; a.teta[C + c] = o2; a.teta[2 * C + c] = o3; }
+    if (lane == 0) meter_state_store(ms, m.state, C, c);
 }
 
 
@@ -519,6 +611,7 @@ struct uhsdr_spectrum_s
     uhsdr_spectrum_plan plan;
     uhsdr_spectrum_plan* d_plan;
     int C, N, L, F, fill;
+    int iq_freq_mode;        // the configuration's (the plan keeps only what it makes of it)
     int D, Nd;               // zoom decimation (1: no zoom), ring samples per call N / D
     hipStream_t stream;
     float *teta, *avg, *carry;
@@ -526,9 +619,9 @@ struct uhsdr_spectrum_s
     ZoomState zs;
     void* arena;
     size_t arena_bytes;
+    uhsdr_meter_handle meter;   // attached signal meter (uhsdr_spectrum_set_meter), or null
+    uhsdr_meter_io meter_io;
 };
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { uhsdr_set_error("%s: %s", #x, hipGetErrorString(e_)); return UHSDR_DEVICE_ERROR; } } while (0)
 
 // LDS floats per wave: the padded frame; with auto I/Q correction also the product scratch and
 // the per-call sums / factors behind it
@@ -588,6 +681,7 @@ extern "C" uhsdr_status uhsdr_spectrum_create(const uhsdr_spectrum_config* cfg, 
         return UHSDR_LENGTH_ERROR;
     }
     h->C = C; h->N = N; h->L = L;
+    h->iq_freq_mode = cfg->iq_freq_mode;
     h->D = D; h->Nd = Nd;
     h->F = Nd >= L ? Nd / L : 1;
     h->stream = (hipStream_t)stream;
@@ -622,10 +716,21 @@ extern "C" uhsdr_status uhsdr_spectrum_create(const uhsdr_spectrum_config* cfg, 
     return UHSDR_OK;
 }
 
+// no meter at 1024 bins (uhsdr_meter_plan_build refuses it), so no such instance
+template <int L, bool AU, bool ZM>
+static void spec_launch_meter(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SpecArgs& sa, const MeterArgs& ma)
+{
+    if constexpr (L != 1024) hipLaunchKernelGGL((spectrum_frames_meter<L, AU, ZM>), grid, block, lds, stream, sa, ma);
+}
+
 extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const int32_t* iq, float* mag, float* avg,
                                                int32_t* frames)
 {
     if (!h || !iq) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    // the epilogue loads and stores the meter's state on this stream: a meter moved to another one
+    // since it was attached would have its own calls race with that
+    if (h->meter && h->meter->stream != h->stream)
+    { uhsdr_set_error("spectrum: the attached meter was moved to another stream"); return UHSDR_ARGUMENT_ERROR; }
     const bool zoom = h->D > 1;
     if (zoom)
     {
@@ -653,7 +758,11 @@ extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const in
     const size_t lds = sizeof(float) * (size_t)SPEC_WAVES * sa.lds_pitch;
     const dim3 grid((h->C + SPEC_WAVES - 1) / SPEC_WAVES), block(64 * SPEC_WAVES);
     const bool completes = h->fill + h->Nd >= h->L;
-#define SPEC_LAUNCH3(LEN, AU, ZM) do { if (completes) hipLaunchKernelGGL((spectrum_frames<LEN, AU, ZM>), grid, block, lds, h->stream, sa); \
+    // a call that completes no frame has nothing to meter
+    const bool metered = h->meter && completes;
+    const MeterArgs ma = metered ? meter_args(h->meter, &h->meter_io, h->F) : MeterArgs{};
+#define SPEC_LAUNCH3(LEN, AU, ZM) do { if (metered) spec_launch_meter<LEN, AU, ZM>(grid, block, lds, h->stream, sa, ma); \
+                                       else if (completes) hipLaunchKernelGGL((spectrum_frames<LEN, AU, ZM>), grid, block, lds, h->stream, sa); \
                                        else hipLaunchKernelGGL((spectrum_accumulate<LEN, AU, ZM>), grid, block, lds, h->stream, sa); } while (0)
 #define SPEC_LAUNCH(LEN) do { if (zoom) SPEC_LAUNCH3(LEN, false, true); else if (au) SPEC_LAUNCH3(LEN, true, false); \
                               else SPEC_LAUNCH3(LEN, false, false); } while (0)
@@ -669,6 +778,29 @@ extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const in
     const int done = (h->fill + h->Nd) / h->L;
     h->fill = (h->fill + h->Nd) % h->L;
     if (frames) *frames = done;
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_spectrum_set_meter(uhsdr_spectrum_handle h, uhsdr_meter_handle meter, const uhsdr_meter_io* io)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (!meter)
+    {
+        h->meter = nullptr;
+        return UHSDR_OK;
+    }
+    if (meter->host) { uhsdr_set_error("spectrum: the meter is a host handle"); return UHSDR_ARGUMENT_ERROR; }
+    const uhsdr_meter_plan& mp = meter->plan;
+    if (mp.fft_len != h->plan.fft_len || mp.magnify != h->plan.magnify || mp.iq_freq_mode != h->iq_freq_mode)
+    {
+        uhsdr_set_error("spectrum: meter built for fft_len %d magnify %d iq_freq_mode %d, spectrum for %d %d %d", mp.fft_len, mp.magnify,
+                        mp.iq_freq_mode, h->plan.fft_len, h->plan.magnify, h->iq_freq_mode);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (meter->C != h->C) { uhsdr_set_error("spectrum: meter of %d channels, spectrum of %d", meter->C, h->C); return UHSDR_ARGUMENT_ERROR; }
+    if (meter->stream != h->stream) { uhsdr_set_error("spectrum: the meter is on another stream"); return UHSDR_ARGUMENT_ERROR; }
+    h->meter = meter;
+    h->meter_io = io ? *io : uhsdr_meter_io{};
     return UHSDR_OK;
 }
 

@@ -5,7 +5,8 @@
 
 ``iq`` is the RX input, [C][N][2] int32 IqSample_t; ``mag`` / ``avg`` are optional [C][F][L] f32
 (F = max(1, N/L)): sd.FFT_MagData and sd.FFT_AVGData after each display frame completed by the
-call; ``nf`` is how many were completed.  All arithmetic runs in libuhsdr_amd.so
+call; ``nf`` is how many were completed.  ``spec.set_meter(meter, dbm=..., s_count=...)`` adds the
+signal meter's outputs per completed frame.  All arithmetic runs in libuhsdr_amd.so
 (uhsdr_spectrum.hip); torch tensors only provide device memory.
 """
 from __future__ import annotations
@@ -50,8 +51,22 @@ class Spectrum:
             C.c_void_p(avg.data_ptr() if avg is not None else 0), C.byref(nf)), "uhsdr_spectrum_process")
         return nf.value
 
+    def set_meter(self, meter, cw_signal=None, **rows) -> None:
+        """Attach a device Meter (uhsdr_amd.meter): every process() then runs the meter's frame on each
+        display frame it completes and writes `rows`, cuda tensors [C][frames_out] named as
+        meter.OUTPUTS; mag and avg may then both be None.  None detaches.  The spectrum keeps a
+        reference to the meter and the rows while attached."""
+        if meter is None:
+            _abi.check(self.lib.uhsdr_spectrum_set_meter(self.handle, None, None), "uhsdr_spectrum_set_meter")
+            self._meter = None
+            return
+        io = meter.io(self.frames_out, cw_signal, **rows)
+        _abi.check(self.lib.uhsdr_spectrum_set_meter(self.handle, meter.handle, C.byref(io)), "uhsdr_spectrum_set_meter")
+        self._meter = (meter, cw_signal, rows)
+
     def close(self) -> None:
         if self.handle:
+            self._meter = None
             self.lib.uhsdr_spectrum_destroy(self.handle)
             self.handle = None
 
