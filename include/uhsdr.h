@@ -1298,6 +1298,108 @@ int32_t      uhsdr_sizeof_meter_plan(void);
    meter is detached or moved back. */
 uhsdr_status uhsdr_spectrum_set_meter(uhsdr_spectrum_handle h, uhsdr_meter_handle meter, const uhsdr_meter_io* io);
 
+/* ---- Display stage (ABI version 9): frames of sd.FFT_AVGData in, scope trace and waterfall line out ----
+ * States 4 and 5 of UiSpectrum_RedrawSpectrum (drivers/ui/lcd/ui_spectrum.c:1467-1517) up to the LCD
+ * calls, one instance per channel, once per completed display frame and in this order:
+ *   UiSpectrum_ScaleFFT (:1258-1292): sig = display_offset + Math_log10f_fast(v) * db_scale per bin, the
+ *     frame's minimum of sig before the clamp at 1, the centre frequency moved to the middle and the
+ *     order flipped (dest[L-1-i] = src[i + L/2], dest[L-1-i] = src[i - L/2]);
+ *   UiSpectrum_ScaleFFT2SpectrumWidth (:1300-1339) when width != fft_len: the fractional reduction in
+ *     place, each pixel a sequential binary32 sum in the firmware's order;
+ *   display_offset -= agc_rate * min / 5 (:1485), the display's sliding AGC: the only state, -80
+ *     (INIT_SPEC_AGC_LEVEL) after create and reset;
+ *   the scope trace (:881): height = (uint16_t)(row < limit ? row : limit), limit = scope_h - 1;
+ *   the waterfall line (:1104, :1120-1128): row * wfall_contrast, >= 64 -> 63, to uint8_t.
+ * The firmware's RedrawType and speed rate limiters are main-loop timing; here every frame gets one
+ * of each.  Exact to the reference: the same bits in all four outputs.
+ *   fft_len            256 or 512 (sd.spec_len); 1024 is UHSDR_ARGUMENT_ERROR, the firmware has no such panel
+ *   width              slayout.scope.w, fft_len / 2 .. fft_len; 0: the firmware's, 256 for 256 and 480 for 512
+ *   spectrum_db_scale  ts.spectrum_db_scale, the index into scope_scaling_factors; 9 (SCOPE_SCALE_NUM)
+ *                      and above fall back to 3 (DB_DIV_ADJUST_DEFAULT) as :1023-1026; default 3
+ *   spectrum_agc_rate  ts.spectrum_agc_rate, 1 .. 50, default 25
+ *   waterfall_contrast ts.waterfall.contrast, 10 .. 225, default 120
+ *   scope_h            slayout.scope.h, 1 .. 65535; 0: the panel's own after a first power-up with scope
+ *                      and waterfall both shown, 21 at 256 and 64 at 512
+ * process_avg: avg = f32 [C][frames][fft_len], frames of FFT_AVGData in natural bin order as
+ * uhsdr_spectrum_process writes them, 16-byte aligned device memory (host memory for _host),
+ * stream-ordered; edge = f32 [C][frames] or null (all 0), see below; io (null: the state only) holds
+ * optional rows, null: not wanted.  state: offset and the last min per channel into host arrays of
+ * num_channels after everything enqueued.
+ * Reference oddities kept: the minimum is taken before the clamp and a NaN never wins it, so a frame of
+ * NaNs leaves min at 100000; a NaN passes the clamp; a NaN height is the limit.  For most widths
+ * below fft_len (480 of 512 among them, not 200 of 256; the plan's reads_edge says which) the
+ * reduction's last pixel reads samples[fft_len], one float behind the scaled row, with a weight of
+ * about 2.7e-5 at 512 -> 480: in the firmware that is float fft_len of arm_cfft_f32's output for the same
+ * frame, the real part of bin fft_len / 2, which nothing overwrites between the transform and state
+ * 4.  That float is `edge`; uhsdr_spectrum_set_display supplies it from the transform itself.
+ * Defined here, not kept: C leaves the conversion of a NaN or of a value outside the target's range
+ * to uint16_t / uint8_t undefined; here a value in (-2^31, 2^31) is truncated to int32 and its low
+ * bits are taken, anything else gives 0, which is what the x86 recording shows.
+ * Not built: the markers and UiSpectrum_UpdateSpectrumPixelParameters, the palettes and RGB565
+ * pixels, the waterfall's line ring with its frequency-shift padding and scrolling, the grid and
+ * the bandwidth highlight, the light scope's line drawing, nr_gain_display, the 1024-point spectrum,
+ * the redraw rate limiters, any FMA mode. */
+typedef struct uhsdr_display_config
+{
+    int32_t fft_len, width;
+    int32_t spectrum_db_scale, spectrum_agc_rate, waterfall_contrast, scope_h;
+    int32_t reserved[10];
+} uhsdr_display_config;
+#define UHSDR_DISPLAY_MAX_WIDTH 512
+/* what UiSpectrum_InitSpectrumDisplayData computes (:955-1089), and the walk of
+   UiSpectrum_ScaleFFT2SpectrumWidth, which does not depend on the data, per output pixel */
+typedef struct uhsdr_display_plan
+{
+    int32_t fft_len, width;
+    int32_t resample;                       /* width != fft_len */
+    int32_t reads_edge;                     /* the walk reads samples[fft_len] */
+    int32_t limit;                          /* scope_h - 1 */
+    float   db_scale;                       /* scope_scaling_factors[].value, times width / fft_len if resampled */
+    float   agc_rate;                       /* spectrum_agc_rate / SPECTRUM_AGC_SCALING */
+    float   wfall_contrast;                 /* (float)contrast / 100.0 */
+    float   full_amount;                    /* (float)fft_len / (float)width */
+    int32_t reserved[7];
+    uint16_t first[UHSDR_DISPLAY_MAX_WIDTH];  /* idx_old when the pixel's inner loop starts */
+    uint8_t  whole[UHSDR_DISPLAY_MAX_WIDTH];  /* samples that loop adds whole, 0 .. 2 */
+    float    amount[UHSDR_DISPLAY_MAX_WIDTH]; /* `amount` when that loop ends, at the split sample */
+} uhsdr_display_plan;
+typedef struct uhsdr_display_io
+{
+    uint16_t* scope;                        /* [C][frames][width] heights */
+    uint8_t*  wfall;                        /* [C][frames][width] palette indices 0 .. 63 */
+    float*    offset;                       /* [C][frames] sd.display_offset after the frame's update */
+    float*    min;                          /* [C][frames] min1 of the frame */
+} uhsdr_display_io;
+typedef struct uhsdr_display_s* uhsdr_display_handle;
+
+void         uhsdr_display_config_default(uhsdr_display_config* cfg);
+uhsdr_status uhsdr_display_plan_build(const uhsdr_display_config* cfg, uhsdr_display_plan* plan);
+uhsdr_status uhsdr_display_create(int32_t num_channels, const uhsdr_display_config* cfg, void* stream, uhsdr_display_handle* out);
+/* the same stage with its state in host memory, for the _host call (no device call) */
+uhsdr_status uhsdr_display_create_host(int32_t num_channels, const uhsdr_display_config* cfg, uhsdr_display_handle* out);
+uhsdr_status uhsdr_display_reset(uhsdr_display_handle h);
+uhsdr_status uhsdr_display_set_stream(uhsdr_display_handle h, void* stream);
+uhsdr_status uhsdr_display_process_avg(uhsdr_display_handle h, const float* avg, const float* edge, int32_t frames,
+                                       const uhsdr_display_io* io);
+uhsdr_status uhsdr_display_process_avg_host(uhsdr_display_handle h, const float* avg, const float* edge, int32_t frames,
+                                            const uhsdr_display_io* io);
+uhsdr_status uhsdr_display_state(uhsdr_display_handle h, float* offset, float* min);
+uhsdr_status uhsdr_display_synchronize(uhsdr_display_handle h);
+uhsdr_status uhsdr_display_destroy(uhsdr_display_handle h);
+int32_t      uhsdr_sizeof_display_config(void);
+int32_t      uhsdr_sizeof_display_plan(void);
+/* The display stage inside the spectrum: with a device display attached, every uhsdr_spectrum_process
+   runs the stage's frame on the average of each display frame it completes, where it lies staged in
+   LDS, after the meter's frame when a meter is attached too, and writes io's rows ([C][F][width] and
+   [C][F], F as for mag / avg; io is copied, null: the state only).  The kernel takes `edge` from its own
+   transform; the caller cannot pass one.  mag and avg may both be null.  A call that completes no
+   frame writes nothing.  The display's state moves exactly as under uhsdr_display_process_avg on the
+   same frames with that edge.  display null detaches: calls then enqueue what they enqueued before.
+   UHSDR_ARGUMENT_ERROR unless fft_len and the channel count of the two agree, the display is a device
+   handle and both are on one stream; the caller keeps the display alive and on that stream while it
+   is attached, as for uhsdr_spectrum_set_meter. */
+uhsdr_status uhsdr_spectrum_set_display(uhsdr_spectrum_handle h, uhsdr_display_handle display, const uhsdr_display_io* io);
+
 #ifdef __cplusplus
 }
 #endif

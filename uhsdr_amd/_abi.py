@@ -200,6 +200,26 @@ class MeterIo(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dbm_cur", "dbmhz_cur", "dbm", "dbmhz", "s_count", "snap_carrier_freq", "cw_signal")]
 
 
+DISPLAY_MAX_WIDTH = 512     # UHSDR_DISPLAY_MAX_WIDTH
+
+
+class DisplayConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fft_len", "width", "spectrum_db_scale", "spectrum_agc_rate", "waterfall_contrast", "scope_h")] + [
+        ("reserved", C.c_int32 * 10)]
+
+
+class DisplayPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("fft_len", "width", "resample", "reads_edge", "limit")] + [
+        (n, C.c_float) for n in ("db_scale", "agc_rate", "wfall_contrast", "full_amount")] + [
+        ("reserved", C.c_int32 * 7), ("first", C.c_uint16 * DISPLAY_MAX_WIDTH), ("whole", C.c_uint8 * DISPLAY_MAX_WIDTH),
+        ("amount", C.c_float * DISPLAY_MAX_WIDTH)]
+
+
+class DisplayIo(C.Structure):
+    """uhsdr_display_io: optional rows, 0: not wanted"""
+    _fields_ = [(n, C.c_void_p) for n in ("scope", "wfall", "offset", "min")]
+
+
 # every exported entry point of include/uhsdr.h: name -> (restype, argtypes)
 SIGNATURES = {
     "uhsdr_rx_config_default": (None, [C.POINTER(RxConfig)]),
@@ -384,6 +404,20 @@ SIGNATURES = {
     "uhsdr_sizeof_meter_config": (C.c_int32, []),
     "uhsdr_sizeof_meter_plan": (C.c_int32, []),
     "uhsdr_spectrum_set_meter": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MeterIo)]),
+    "uhsdr_display_config_default": (None, [C.POINTER(DisplayConfig)]),
+    "uhsdr_display_plan_build": (C.c_int, [C.POINTER(DisplayConfig), C.POINTER(DisplayPlan)]),
+    "uhsdr_display_create": (C.c_int, [C.c_int32, C.POINTER(DisplayConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_display_create_host": (C.c_int, [C.c_int32, C.POINTER(DisplayConfig), C.POINTER(C.c_void_p)]),
+    "uhsdr_display_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_display_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_display_process_avg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DisplayIo)]),
+    "uhsdr_display_process_avg_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DisplayIo)]),
+    "uhsdr_display_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhsdr_display_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_display_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_sizeof_display_config": (C.c_int32, []),
+    "uhsdr_sizeof_display_plan": (C.c_int32, []),
+    "uhsdr_spectrum_set_display": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DisplayIo)]),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -447,6 +481,8 @@ def load(path: str | None = None) -> C.CDLL:
         raise RuntimeError("ctypes layout of uhsdr_spectrum_config / _plan does not match include/uhsdr.h")
     if not variant and (lib.uhsdr_sizeof_meter_config() != C.sizeof(MeterConfig) or lib.uhsdr_sizeof_meter_plan() != C.sizeof(MeterPlan)):
         raise RuntimeError("ctypes layout of uhsdr_meter_config / _plan does not match include/uhsdr.h")
+    if not variant and (lib.uhsdr_sizeof_display_config() != C.sizeof(DisplayConfig) or lib.uhsdr_sizeof_display_plan() != C.sizeof(DisplayPlan)):
+        raise RuntimeError("ctypes layout of uhsdr_display_config / _plan does not match include/uhsdr.h")
     if path is None:
         _lib = lib
     return lib

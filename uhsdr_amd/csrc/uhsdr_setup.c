@@ -1020,3 +1020,94 @@ uhsdr_status uhsdr_meter_plan_build(const uhsdr_meter_config* cfg, uhsdr_meter_p
 
 int32_t uhsdr_sizeof_meter_config(void) { return (int32_t)sizeof(uhsdr_meter_config); }
 int32_t uhsdr_sizeof_meter_plan(void) { return (int32_t)sizeof(uhsdr_meter_plan); }
+
+/* ---- display stage: what UiSpectrum_InitSpectrumDisplayData computes (ui_spectrum.c:955-1089) and the
+   walk of UiSpectrum_ScaleFFT2SpectrumWidth (:1300-1339), which never looks at the data ---- */
+#include "uhsdr_display.h"
+#include "uhsdr_display_tables.h"
+
+#define DISPLAY_SCALE_NUM 9                 /* SCOPE_SCALE_NUM, ui_spectrum.h:57 */
+#define DISPLAY_DB_DIV_DEFAULT 3            /* DB_DIV_ADJUST_DEFAULT = DB_DIV_10, :62 */
+#define DISPLAY_AGC_SCALING 25              /* SPECTRUM_AGC_SCALING, :156 */
+
+void uhsdr_display_config_default(uhsdr_display_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->fft_len = 256;
+    cfg->spectrum_db_scale = DISPLAY_DB_DIV_DEFAULT;
+    cfg->spectrum_agc_rate = 25;                 /* SPECTRUM_SCOPE_AGC_DEFAULT, ui_spectrum.h:149 */
+    cfg->waterfall_contrast = 120;               /* WATERFALL_CONTRAST_DEFAULT, :90 */
+}
+
+uhsdr_status uhsdr_display_plan_build(const uhsdr_display_config* cfg, uhsdr_display_plan* p)
+{
+    if (!cfg || !p) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->fft_len != 256 && cfg->fft_len != 512)
+    { uhsdr_set_error("display: fft_len %d: need 256 or 512 (the firmware has no panel of 1024 bins)", cfg->fft_len); return UHSDR_ARGUMENT_ERROR; }
+    const int L = cfg->fft_len;
+    const int W = cfg->width ? cfg->width : (L == 256 ? 256 : 480);
+    if (W < L / 2 || W > L)
+    { uhsdr_set_error("display: width %d outside %d..%d (fft_len / 2 .. fft_len)", W, L / 2, L); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->spectrum_db_scale < 0)
+    { uhsdr_set_error("display: spectrum_db_scale %d is negative", cfg->spectrum_db_scale); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->spectrum_agc_rate < 1 || cfg->spectrum_agc_rate > 50)
+    { uhsdr_set_error("display: spectrum_agc_rate %d outside 1..50", cfg->spectrum_agc_rate); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->waterfall_contrast < 10 || cfg->waterfall_contrast > 225)
+    { uhsdr_set_error("display: waterfall_contrast %d outside 10..225", cfg->waterfall_contrast); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->scope_h < 0 || cfg->scope_h > 65535)
+    { uhsdr_set_error("display: scope_h %d outside 0..65535", cfg->scope_h); return UHSDR_ARGUMENT_ERROR; }
+    memset(p, 0, sizeof *p);
+    p->fft_len = L;
+    p->width = W;
+    p->resample = W != L;
+    /* slayout.scope.h after UiSpectrum_CalculateLayout on a first power-up, scope and waterfall shown
+       (ui_spectrum.c:57-128 on ui_lcd_layouts.c:226-228 and :295-296) */
+    const int scope_h = cfg->scope_h ? cfg->scope_h : (L == 256 ? 21 : 64);
+    p->limit = (uint16_t)(scope_h - 1);          /* const uint16_t spec_height_limit = sd.scope_size - 1, :691 */
+    const int scale = cfg->spectrum_db_scale >= DISPLAY_SCALE_NUM ? DISPLAY_DB_DIV_DEFAULT : cfg->spectrum_db_scale;   /* :1023-1026 */
+    copy_bits(&p->db_scale, &uhsdr_display_scaling_factors[scale], 1);
+    if (p->resample) p->db_scale *= (float)W / (float)L;                         /* :1033-1036 */
+    p->agc_rate = ((float)cfg->spectrum_agc_rate) / DISPLAY_AGC_SCALING;         /* :988 */
+    p->wfall_contrast = (float)((double)(float)cfg->waterfall_contrast / 100.0); /* :1081 */
+    p->full_amount = (float)L / (float)W;
+    if (!p->resample) return UHSDR_OK;
+    /* the walk: per pixel where its loop starts, how many samples the loop adds whole, and `amount`
+       when it ends.  The firmware works in place, so every index a pixel reads must not have been
+       written by an earlier pixel: first[x] >= x (pixel x is written after its own reads) */
+    float amount = p->full_amount;
+    int idx_old = 0;
+    for (int x = 0; x < W; x++)
+    {
+        int n = 0;
+        if (idx_old < x)
+        {
+            uhsdr_set_error("display: %d -> %d: pixel %d reads sample %d after it was overwritten", L, W, x, idx_old);
+            return UHSDR_ARGUMENT_ERROR;
+        }
+        p->first[x] = (uint16_t)idx_old;
+        while (amount >= 1)
+        {
+            idx_old++;
+            n++;
+            amount = (float)((double)amount - 1.0);
+        }
+        if (n > 2 || idx_old > L)
+        {
+            uhsdr_set_error("display: %d -> %d: pixel %d takes %d whole samples up to index %d", L, W, x, n, idx_old);
+            return UHSDR_ARGUMENT_ERROR;
+        }
+        p->whole[x] = (uint8_t)n;
+        p->amount[x] = amount;
+        if (idx_old == L) p->reads_edge = 1;
+        if (x + 1 < W)
+        {
+            idx_old++;
+            amount = p->full_amount - (1 - amount);
+        }
+    }
+    return UHSDR_OK;
+}
+
+int32_t uhsdr_sizeof_display_config(void) { return (int32_t)sizeof(uhsdr_display_config); }
+int32_t uhsdr_sizeof_display_plan(void) { return (int32_t)sizeof(uhsdr_display_plan); }

@@ -26,6 +26,7 @@
 #include "uhsdr_dsp.h"
 #include "uhsdr_cfft.h"
 #include "uhsdr_meter_host.h"
+#include "uhsdr_display_host.h"
 
 namespace {
 
@@ -185,11 +186,16 @@ __device__ __forceinline__ SpecParams spec_params(const uhsdr_spectrum_plan* __r
 // stages in registers, the middle radix-8 stage through LDS, the last stage into registers,
 // the bit reversal as the output bin of each butterfly result, then magnitude and average
 // (ui_spectrum.c:1405, 1432-1446).  METER: then the signal meter's frame (uhsdr_meter.h) on the
-// magnitudes where they lie staged, with the channel's meter state `ms` in registers.
-template <int L, bool METER = false>
+// magnitudes where they lie staged, with the channel's meter state `ms` in registers.  DISPLAY: then
+// the display stage's frame (uhsdr_display.h) on the staged average, with the scaled row over the
+// magnitudes, which nothing reads any more, the channel's display_offset `doff` in a register, and
+// `edge` from the transform itself: float L of arm_cfft_f32's output is the real part of bin L / 2,
+// which one lane holds as y[r][k].x; it goes to all lanes by a ballot and a shuffle.
+template <int L, bool METER = false, bool DISPLAY = false>
 __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], float2* X, const float* __restrict__ tw,
                                                float (&av)[SpecGeom<L>::R3][8], float f, const SpecArgs& a, int c,
-                                               int frame, int lane, const MeterArgs* m = nullptr, meter_state* ms = nullptr)
+                                               int frame, int lane, const MeterArgs* m = nullptr, meter_state* ms = nullptr,
+                                               const DisplayArgs* d = nullptr, float* doff = nullptr, float* dmin = nullptr)
 {
     using G = SpecGeom<L>;
     constexpr int NBF = G::NBF, R3 = G::R3;
@@ -198,6 +204,8 @@ __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], floa
     cfft_core<L>(z, X, tw, &P->tw_lane[0][0][0], lane, y);
     wave_sync();                                 // the frame is consumed: its LDS now stages the outputs
     float* O = (float*)X;                        // [2][L] in bin order
+    float edge = 0.0f;
+    bool edge_here = false;
 #pragma unroll
     for (int r = 0; r < R3; ++r)
     {
@@ -220,6 +228,8 @@ __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], floa
                 const int bin = (bw[k >> 1] >> (16 * (k & 1))) & 0xffff;
                 O[bin] = mg;
                 O[L + bin] = s;
+                if constexpr (DISPLAY)
+                    if (bin == L / 2) { edge = y[r][k].x; edge_here = true; }
             }
         }
     }
@@ -238,6 +248,13 @@ __device__ __forceinline__ void spectrum_frame(float2 (&z)[SpecGeom<L>::K], floa
         const size_t at = (size_t)c * a.F + frame;
         meter_wave_frame(m->plan, *ms, O, m->io.cw_signal ? m->io.cw_signal[at] : 0, lane);
         if (lane == 0) meter_write(m->io, *ms, at);
+    }
+    if constexpr (DISPLAY)
+    {
+        const unsigned long long holder = __ballot(edge_here);      // exactly one lane: iperm is a permutation
+        edge = __shfl(edge, __ffsll(holder) - 1, 64);
+        wave_sync();                             // the magnitudes' readers are done: the scaled row lands on them
+        *dmin = display_wave_frame(d->plan, *doff, O + L, O, edge, (size_t)c * a.F + frame, d->io, lane);
     }
     wave_sync();                                 // staged outputs read before the next frame lands
 }
@@ -270,7 +287,8 @@ __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_accumulate(SpecArgs 
 }
 
 // Calls that complete frames: every segment ends a frame; the first may start from the carry.
-// spectrum_frames_meter below is this walk again with the signal meter in it: a change here belongs there too.
+// spectrum_frames_meter and spectrum_frames_display below are this walk again with the signal meter and
+// the display stage in it: a change here belongs there too.
 template <int L, bool AUTO, bool ZM>
 __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames(SpecArgs a)
 {
@@ -428,6 +446,93 @@ __global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames_meter(SpecArg
     if (AUTO && lane == 0) { a.teta[c] = o1; a.teta[C + c] = o2; a.teta[2 * C + c] = o3; }
     if (lane == 0) meter_state_store(ms, m.state, C, c);
 }
+
+
+// spectrum_frames with the display stage attached (uhsdr_spectrum_set_display), METER: and a signal
+// meter: the same walk once more, with the channel's display_offset in a register beside the
+// averages and the display's frame run on every completed frame's staged average, after the meter's
+// (spectrum_frame<L, METER, true>).  Kernels of their own for the reason given above: the instances
+// without a display keep the code they had.
+template <int L, bool AUTO, bool ZM, bool METER>
+__global__ void __launch_bounds__(64 * SPEC_WAVES) spectrum_frames_display(SpecArgs a, MeterArgs m, DisplayArgs d)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    using G = SpecGeom<L>;
+    constexpr int K = G::K, NBF = G::NBF, R3 = G::R3;
+    const uhsdr_spectrum_plan* __restrict__ P = a.plan;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * SPEC_WAVES + w;
+    if (c >= a.C) return;                        // whole wave; no workgroup barrier below
+    float* S = smem + w * a.lds_pitch;           // auto-I/Q products, then the frame
+    float2* X = (float2*)S;
+    float* T = S + G::REGION;                    // used only with auto I/Q correction
+    const float* __restrict__ tw = P->twiddle;
+    const SpecParams sp = spec_params<L>(P);
+    const float f = P->filt_factor;
+    const int C = a.C, N = a.N;
+    const size_t row = (size_t)c * L;
+
+    // the final-stage outputs this lane owns: positions 8q + k, q = lane + 64r; their running
+    // averages stay in registers (state kept in position order, bins via plan->iperm)
+    float av[R3][8];
+#pragma unroll
+    for (int r = 0; r < R3; ++r)
+    {
+        const int q = lane + 64 * r;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) av[r][k] = q < NBF ? a.avg_state[row + 8 * q + k] : 0.0f;
+    }
+    float o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+    if (AUTO) { o1 = a.teta[c]; o2 = a.teta[C + c]; o3 = a.teta[2 * C + c]; }
+    meter_state ms;
+    if constexpr (METER) meter_state_load(ms, m.state, C, c);
+    float doff = d.state[c], dmin = d.state[C + c];
+    using SrcT = typename std::conditional<ZM, float2, int2>::type;
+    const SrcT* __restrict__ src;
+    if constexpr (ZM) src = a.zq + (size_t)c * a.ld;
+    else src = a.iq + (size_t)c * a.ld;
+
+    int n0 = 0, frame = 0;
+    if (a.fill0)
+    {
+        // ---- the frame begun in earlier calls ----
+        const float2* __restrict__ carry = (const float2*)a.carry + (size_t)c * L;
+        float2 z[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+        {
+            const int p = lane + 64 * k;
+            z[k] = carry[p < a.fill0 ? p : 0];
+        }
+        produce<L, true, AUTO && !ZM, ZM>(z, src, a.fill0, L, sp, S, T, o1, o2, o3, lane);
+        spectrum_frame<L, METER, true>(z, X, tw, av, f, a, c, frame, lane, &m, &ms, &d, &doff, &dmin);
+        n0 = L - a.fill0;
+        ++frame;
+    }
+    for (; n0 < N; n0 += L, ++frame)
+    {
+        // per-frame reloads (L1-resident) instead of loop-invariant registers: keeps the window
+        // and the twiddles from being hoisted out of the frame loop into VGPRs
+        SpecParams spf = sp;
+        const float* __restrict__ twf = tw;
+        asm volatile("" : "+s"(spf.win), "+s"(twf));
+        float2 z[K];
+        produce<L, false, AUTO && !ZM, ZM>(z, src + n0, 0, L, spf, S, T, o1, o2, o3, lane);
+        spectrum_frame<L, METER, true>(z, X, twf, av, f, a, c, frame, lane, &m, &ms, &d, &doff, &dmin);
+    }
+#pragma unroll
+    for (int r = 0; r < R3; ++r)
+    {
+        const int q = lane + 64 * r;
+        if (q < NBF)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a.avg_state[row + 8 * q + k] = av[r][k];
+    }
+    if (AUTO && lane == 0) { a.teta[c] = o1; a.teta[C + c] = o2; a.teta[2 * C + c] = o3; }
+    if (METER && lane == 0) meter_state_store(ms, m.state, C, c);
+    if (lane == 0) { d.state[c] = doff; d.state[C + c] = dmin; }
+}
+
 
 
 // ---- zoom producer (AudioDriver_SpectrumZoomProcessSamples, audio_driver.c:1860-1909) ----
@@ -621,6 +726,8 @@ struct uhsdr_spectrum_s
     size_t arena_bytes;
     uhsdr_meter_handle meter;   // attached signal meter (uhsdr_spectrum_set_meter), or null
     uhsdr_meter_io meter_io;
+    uhsdr_display_handle display;   // attached display stage (uhsdr_spectrum_set_display), or null
+    uhsdr_display_io display_io;
 };
 
 // LDS floats per wave: the padded frame; with auto I/Q correction also the product scratch and
@@ -723,6 +830,18 @@ static void spec_launch_meter(dim3 grid, dim3 block, size_t lds, hipStream_t str
     if constexpr (L != 1024) hipLaunchKernelGGL((spectrum_frames_meter<L, AU, ZM>), grid, block, lds, stream, sa, ma);
 }
 
+// nor a display (uhsdr_display_plan_build refuses 1024 as well)
+template <int L, bool AU, bool ZM>
+static void spec_launch_display(dim3 grid, dim3 block, size_t lds, hipStream_t stream, bool metered, const SpecArgs& sa, const MeterArgs& ma,
+                                const DisplayArgs& da)
+{
+    if constexpr (L != 1024)
+    {
+        if (metered) hipLaunchKernelGGL((spectrum_frames_display<L, AU, ZM, true>), grid, block, lds, stream, sa, ma, da);
+        else hipLaunchKernelGGL((spectrum_frames_display<L, AU, ZM, false>), grid, block, lds, stream, sa, ma, da);
+    }
+}
+
 extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const int32_t* iq, float* mag, float* avg,
                                                int32_t* frames)
 {
@@ -731,6 +850,8 @@ extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const in
     // since it was attached would have its own calls race with that
     if (h->meter && h->meter->stream != h->stream)
     { uhsdr_set_error("spectrum: the attached meter was moved to another stream"); return UHSDR_ARGUMENT_ERROR; }
+    if (h->display && h->display->stream != h->stream)
+    { uhsdr_set_error("spectrum: the attached display was moved to another stream"); return UHSDR_ARGUMENT_ERROR; }
     const bool zoom = h->D > 1;
     if (zoom)
     {
@@ -761,7 +882,11 @@ extern "C" uhsdr_status uhsdr_spectrum_process(uhsdr_spectrum_handle h, const in
     // a call that completes no frame has nothing to meter
     const bool metered = h->meter && completes;
     const MeterArgs ma = metered ? meter_args(h->meter, &h->meter_io, h->F) : MeterArgs{};
-#define SPEC_LAUNCH3(LEN, AU, ZM) do { if (metered) spec_launch_meter<LEN, AU, ZM>(grid, block, lds, h->stream, sa, ma); \
+    // nor anything to display
+    const bool shown = h->display && completes;
+    const DisplayArgs da = shown ? display_args(h->display, &h->display_io, h->F) : DisplayArgs{};
+#define SPEC_LAUNCH3(LEN, AU, ZM) do { if (shown) spec_launch_display<LEN, AU, ZM>(grid, block, lds, h->stream, metered, sa, ma, da); \
+                                       else if (metered) spec_launch_meter<LEN, AU, ZM>(grid, block, lds, h->stream, sa, ma); \
                                        else if (completes) hipLaunchKernelGGL((spectrum_frames<LEN, AU, ZM>), grid, block, lds, h->stream, sa); \
                                        else hipLaunchKernelGGL((spectrum_accumulate<LEN, AU, ZM>), grid, block, lds, h->stream, sa); } while (0)
 #define SPEC_LAUNCH(LEN) do { if (zoom) SPEC_LAUNCH3(LEN, false, true); else if (au) SPEC_LAUNCH3(LEN, true, false); \
@@ -801,6 +926,27 @@ extern "C" uhsdr_status uhsdr_spectrum_set_meter(uhsdr_spectrum_handle h, uhsdr_
     if (meter->stream != h->stream) { uhsdr_set_error("spectrum: the meter is on another stream"); return UHSDR_ARGUMENT_ERROR; }
     h->meter = meter;
     h->meter_io = io ? *io : uhsdr_meter_io{};
+    return UHSDR_OK;
+}
+
+extern "C" uhsdr_status uhsdr_spectrum_set_display(uhsdr_spectrum_handle h, uhsdr_display_handle display, const uhsdr_display_io* io)
+{
+    if (!h) { uhsdr_set_error("null handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (!display)
+    {
+        h->display = nullptr;
+        return UHSDR_OK;
+    }
+    if (display->host) { uhsdr_set_error("spectrum: the display is a host handle"); return UHSDR_ARGUMENT_ERROR; }
+    if (display->plan.fft_len != h->plan.fft_len)
+    {
+        uhsdr_set_error("spectrum: display built for fft_len %d, spectrum for %d", display->plan.fft_len, h->plan.fft_len);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    if (display->C != h->C) { uhsdr_set_error("spectrum: display of %d channels, spectrum of %d", display->C, h->C); return UHSDR_ARGUMENT_ERROR; }
+    if (display->stream != h->stream) { uhsdr_set_error("spectrum: the display is on another stream"); return UHSDR_ARGUMENT_ERROR; }
+    h->display = display;
+    h->display_io = io ? *io : uhsdr_display_io{};
     return UHSDR_OK;
 }
 

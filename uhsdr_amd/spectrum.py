@@ -6,7 +6,8 @@
 ``iq`` is the RX input, [C][N][2] int32 IqSample_t; ``mag`` / ``avg`` are optional [C][F][L] f32
 (F = max(1, N/L)): sd.FFT_MagData and sd.FFT_AVGData after each display frame completed by the
 call; ``nf`` is how many were completed.  ``spec.set_meter(meter, dbm=..., s_count=...)`` adds the
-signal meter's outputs per completed frame.  All arithmetic runs in libuhsdr_amd.so
+signal meter's outputs per completed frame, ``spec.set_display(display, scope=..., wfall=...)`` the
+display stage's scope trace and waterfall line.  All arithmetic runs in libuhsdr_amd.so
 (uhsdr_spectrum.hip); torch tensors only provide device memory.
 """
 from __future__ import annotations
@@ -64,9 +65,24 @@ class Spectrum:
         _abi.check(self.lib.uhsdr_spectrum_set_meter(self.handle, meter.handle, C.byref(io)), "uhsdr_spectrum_set_meter")
         self._meter = (meter, cw_signal, rows)
 
+    def set_display(self, display, **rows) -> None:
+        """Attach a device Display (uhsdr_amd.display): every process() then runs the display stage's
+        frame on each display frame it completes, after the meter's, and writes `rows`, cuda tensors
+        named as display.OUTPUTS ([C][frames_out][width] and [C][frames_out]); mag and avg may then
+        both be None.  None detaches.  The spectrum keeps a reference to the display and the rows
+        while attached."""
+        if display is None:
+            _abi.check(self.lib.uhsdr_spectrum_set_display(self.handle, None, None), "uhsdr_spectrum_set_display")
+            self._display = None
+            return
+        io = display.io(self.frames_out, **rows)
+        _abi.check(self.lib.uhsdr_spectrum_set_display(self.handle, display.handle, C.byref(io)), "uhsdr_spectrum_set_display")
+        self._display = (display, rows)
+
     def close(self) -> None:
         if self.handle:
             self._meter = None
+            self._display = None
             self.lib.uhsdr_spectrum_destroy(self.handle)
             self.handle = None
 
