@@ -22,10 +22,10 @@ ORACLE  := oracle/build/libuhsdr_oracle.so
 OBJDIR  := uhsdr_amd/build
 
 HOST_SRCS := uhsdr_amd/csrc/uhsdr_setup.c uhsdr_amd/csrc/uhsdr_filter_tables.c
-HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip uhsdr_amd/csrc/uhsdr_nr.hip uhsdr_amd/csrc/uhsdr_nb.hip uhsdr_amd/csrc/uhsdr_meter.hip uhsdr_amd/csrc/uhsdr_display.hip
+HIP_SRCS  := uhsdr_amd/csrc/uhsdr_rx.hip uhsdr_amd/csrc/uhsdr_tx.hip uhsdr_amd/csrc/uhsdr_spectrum.hip uhsdr_amd/csrc/uhsdr_i2s.hip uhsdr_amd/csrc/uhsdr_fir.hip uhsdr_amd/csrc/uhsdr_cwdec.hip uhsdr_amd/csrc/uhsdr_rtty.hip uhsdr_amd/csrc/uhsdr_psk.hip uhsdr_amd/csrc/uhsdr_digimod.hip uhsdr_amd/csrc/uhsdr_cwgen.hip uhsdr_amd/csrc/uhsdr_nr.hip uhsdr_amd/csrc/uhsdr_nb.hip uhsdr_amd/csrc/uhsdr_meter.hip uhsdr_amd/csrc/uhsdr_display.hip uhsdr_amd/csrc/uhsdr_wfall.hip
 HOST_OBJS := $(patsubst uhsdr_amd/csrc/%.c,$(OBJDIR)/%.o,$(HOST_SRCS))
 HIP_OBJS  := $(patsubst uhsdr_amd/csrc/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
-HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_arena.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h uhsdr_amd/csrc/uhsdr_nr.h uhsdr_amd/csrc/uhsdr_nr_tables.h uhsdr_amd/csrc/uhsdr_libm_expf.h uhsdr_amd/csrc/uhsdr_nb.h uhsdr_amd/csrc/uhsdr_meter.h uhsdr_amd/csrc/uhsdr_meter_host.h uhsdr_amd/csrc/uhsdr_meter_tables.h uhsdr_amd/csrc/uhsdr_log10f_fast.h uhsdr_amd/csrc/uhsdr_display.h uhsdr_amd/csrc/uhsdr_display_host.h uhsdr_amd/csrc/uhsdr_display_tables.h
+HDRS := uhsdr_amd/csrc/uhsdr_rx_variants.inc include/uhsdr.h uhsdr_amd/csrc/uhsdr_internal.h uhsdr_amd/csrc/uhsdr_dsp.h uhsdr_amd/csrc/uhsdr_libm.h uhsdr_amd/csrc/uhsdr_cfft.h uhsdr_amd/csrc/uhsdr_cwdec.h uhsdr_amd/csrc/uhsdr_rtty.h uhsdr_amd/csrc/uhsdr_psk.h uhsdr_amd/csrc/uhsdr_digiq.h uhsdr_amd/csrc/uhsdr_rttymod.h uhsdr_amd/csrc/uhsdr_pskmod.h uhsdr_amd/csrc/uhsdr_arena.h uhsdr_amd/csrc/uhsdr_digimod_host.h uhsdr_amd/csrc/uhsdr_cwgen.h uhsdr_amd/csrc/uhsdr_cwgen_host.h uhsdr_amd/csrc/uhsdr_cwgen_tables.h uhsdr_amd/csrc/uhsdr_nr.h uhsdr_amd/csrc/uhsdr_nr_tables.h uhsdr_amd/csrc/uhsdr_libm_expf.h uhsdr_amd/csrc/uhsdr_nb.h uhsdr_amd/csrc/uhsdr_meter.h uhsdr_amd/csrc/uhsdr_meter_host.h uhsdr_amd/csrc/uhsdr_meter_tables.h uhsdr_amd/csrc/uhsdr_log10f_fast.h uhsdr_amd/csrc/uhsdr_display.h uhsdr_amd/csrc/uhsdr_display_host.h uhsdr_amd/csrc/uhsdr_display_tables.h uhsdr_amd/csrc/uhsdr_wfall.h uhsdr_amd/csrc/uhsdr_wfall_tables.h
 
 EXAMPLE := examples/build/rx_batch
 
@@ -84,9 +84,9 @@ $(EXAMPLE): examples/rx_batch.c include/uhsdr.h $(LIB) | examples/build
 ref:
 	$(MAKE) -C oracle/ref
 
-# re-record every module fixture from the reference (tools/recording.py) and the four generated
+# re-record every module fixture from the reference (tools/recording.py) and the five generated
 # table headers, and fail where a committed file would change; nothing is written
-MAKERS := cwtext rtty psk digimod cwgen nr nb meter display
+MAKERS := cwtext rtty psk digimod cwgen nr nb meter display wfall
 fixtures-check:
 	set -e; for m in $(MAKERS); do python3 tools/$$m/make_$${m}_golden.py --check; done
 	python3 tools/nr/make_nr_chain_golden.py --check
@@ -94,6 +94,7 @@ fixtures-check:
 	python3 tools/nr/gen_nr_tables.py --check
 	python3 tools/meter/gen_meter_tables.py --check
 	python3 tools/display/gen_display_tables.py --check
+	python3 tools/wfall/gen_wfall_tables.py --check
 
 include tools/sanitize.mk
 

@@ -1335,8 +1335,8 @@ uhsdr_status uhsdr_spectrum_set_meter(uhsdr_spectrum_handle h, uhsdr_meter_handl
  * Defined here, not kept: C leaves the conversion of a NaN or of a value outside the target's range
  * to uint16_t / uint8_t undefined; here a value in (-2^31, 2^31) is truncated to int32 and its low
  * bits are taken, anything else gives 0, which is what the x86 recording shows.
- * Not built: the markers and UiSpectrum_UpdateSpectrumPixelParameters, the palettes and RGB565
- * pixels, the waterfall's line ring with its frequency-shift padding and scrolling, the grid and
+ * Behind the byte line: uhsdr_wfall_* below (the waterfall's line ring with its frequency-shift
+ * padding and scrolling, the palettes and RGB565 pixels, the markers).  Not built: the grid and
  * the bandwidth highlight, the light scope's line drawing, nr_gain_display, the 1024-point spectrum,
  * the redraw rate limiters, any FMA mode. */
 typedef struct uhsdr_display_config
@@ -1399,6 +1399,107 @@ int32_t      uhsdr_sizeof_display_plan(void);
    handle and both are on one stream; the caller keeps the display alive and on that stream while it
    is attached, as for uhsdr_spectrum_set_meter. */
 uhsdr_status uhsdr_spectrum_set_display(uhsdr_spectrum_handle h, uhsdr_display_handle display, const uhsdr_display_io* io);
+
+/* ---- Waterfall image (ABI version 9): byte lines of palette indices in, the panel's RGB565 rows out ----
+ * The rest of UiSpectrum_DrawWaterfall (drivers/ui/lcd/ui_spectrum.c:1099-1256) behind the byte line,
+ * with what it takes from UiSpectrum_InitSpectrumDisplayData (:990-1070) and
+ * UiSpectrum_UpdateSpectrumPixelParameters (:244-350), one instance per channel:
+ *   the ring: frame k's line goes to ring line wfall_line % wfall_size with sd.FFT_frequency beside it
+ *     (:1118-1130); wfall_size is the height, halved if height * width exceeds the firmware's 20480
+ *     bytes of ring and cut to 20480 / width if half does not fit either (:1046-1064); repeat =
+ *     height / wfall_size (:1070);
+ *   the counters (:1131-1146): doubleLineStart counts down from `repeat` and wfall_line advances only
+ *     when it wraps, so a ring line is written by repeat + 1 consecutive frames and keeps the last;
+ *     wfall_line_update counts modulo vert_step_size and only a frame that brings it to 0 draws;
+ *   a drawing (:1150-1253) walks back through the ring from the line before wfall_line; per ring line
+ *     offset_pixel = (int32)((float)(int32)(line's frequency - the frame's) / hz_per_pixel), replaced
+ *     by width - 1 when |offset_pixel| >= width (either sign); the line is moved right by offset_pixel
+ *     with black (0) where nothing comes, its bytes go through the palette, the marker columns are
+ *     overwritten with entry 64; the first ring line is put repeat + 1 - doubleLineStart times, every
+ *     other repeat + 1 times, height rows in all.
+ * Exact to the reference: the same bits in every pixel.
+ *   width              slayout.wfall.w, 128 .. 512 (what the display stage writes)
+ *   height             slayout.wfall.h, 1 .. 255
+ *   color_scheme       ts.waterfall.color_scheme, 0 .. 4: grey, hot-cold, rainbow, blue, inverse grey
+ *   vert_step_size     ts.waterfall.vert_step_size, 1 .. 5
+ *   marker_colour      RGB565, 0 .. 65535: sd.scope_centre_grid_colour_active, palette entry 64
+ *   magnify            sd.magnify, 0 .. 5: hz_per_pixel = 48000 / (2^magnify * width)
+ *   iq_freq_mode       UHSDR_IQ_CONV_*: where the receive carrier stands when magnify is 0
+ *   dmod_mode, digital_mode (UHSDR_DIGITAL_MODE_*), cw_lsb, digi_lsb, cw_sidetone_freq (0 .. 65535),
+ *   rtty_shift_idx (0 .. 5), psk_speed_idx (0 .. 2)    which markers there are (:292-335): CW one at
+ *                      the sidetone, RTTY two at 915 Hz and 915 Hz + shift, BPSK two at 500 Hz -+ speed / 2,
+ *                      anything else one at the carrier
+ *   tx_minus_rx_hz     TX dial minus RX dial frequency, which moves every marker (:287)
+ * process_lines: lines = u8 [C][frames][width], exactly the wfall row of uhsdr_display_io; center_hz =
+ * u32 [C][frames], sd.FFT_frequency of each frame, or null (every frame at 0: nothing is shifted);
+ * device memory (host memory for _host), stream-ordered.  io (null: ring and counters only):
+ *   image  u16 [C][height][width]: the rows of the last drawing inside this call in the order the
+ *          firmware hands them to the panel, row 0 the newest line; untouched if no frame of the call drew
+ *   drawn  u8 [C][frames]: 1 where the frame drew
+ * The counters never look at the data and are the handle's, one set for all channels, advanced on
+ * the host at enqueue; state reports them.  Per channel: the ring and its frequencies, zero after
+ * create and reset.
+ * Defined here, not kept: doubleLineStart, a function static the firmware never clears, is 0 after
+ * create and reset; a ring byte above 64 reads behind the palette in the firmware and is colour 0
+ * here (64 is the marker colour in both); a marker position converts to uint16_t as the display
+ * stage converts (truncated to int32, low bits; what x86 records); ts.ptt_req is always false.
+ * UHSDR_ARGUMENT_ERROR: a value outside the ranges above; a configuration whose wfall_size exceeds
+ * the 80 entries of sd.waterfall_frequencies (the firmware would write behind that array: width 128
+ * with a height of 81 .. 255 does, widths from 256 on never do); image not 2-byte aligned;
+ * lines and image overlapping.
+ * Not built: the scope's drawing (grid, bandwidth highlight, light scope), an image per frame,
+ * uhsdr_i2s_* with it, any fusion into the spectrum kernel. */
+typedef struct uhsdr_wfall_config
+{
+    int32_t width, height;
+    int32_t color_scheme, vert_step_size, marker_colour;
+    int32_t magnify, iq_freq_mode, dmod_mode, digital_mode, cw_lsb, digi_lsb;
+    int32_t cw_sidetone_freq, rtty_shift_idx, psk_speed_idx;
+    int32_t tx_minus_rx_hz;
+    int32_t reserved[9];
+} uhsdr_wfall_config;
+#define UHSDR_WFALL_COLOURS 65              /* NUMBER_WATERFALL_COLOURS + 1 */
+#define UHSDR_WFALL_MAX_MARKER 3            /* SPECTRUM_MAX_MARKER */
+#define UHSDR_WFALL_MAX_LINES 80            /* entries of sd.waterfall_frequencies */
+#define UHSDR_WFALL_RING_BYTES 20480        /* sizeof sd.waterfall */
+typedef struct uhsdr_wfall_plan
+{
+    int32_t width, height;
+    int32_t wfall_size;                     /* ring lines */
+    int32_t repeat;                         /* sd.repeatWaterfallLine */
+    int32_t vert_step_size;
+    int32_t marker_num;
+    float   hz_per_pixel;
+    float   rx_carrier_pos;
+    float   marker_pos[UHSDR_WFALL_MAX_MARKER];      /* unused ones: width */
+    uint16_t marker_pixel[UHSDR_WFALL_MAX_MARKER];   /* (uint16_t)marker_pos of the markers in use; unused ones: width */
+    uint16_t colours[UHSDR_WFALL_COLOURS];           /* sd.waterfall_colours */
+    int32_t reserved[8];
+} uhsdr_wfall_plan;
+typedef struct uhsdr_wfall_io
+{
+    uint16_t* image;                        /* [C][height][width] */
+    uint8_t*  drawn;                        /* [C][frames] */
+} uhsdr_wfall_io;
+typedef struct uhsdr_wfall_s* uhsdr_wfall_handle;
+
+void         uhsdr_wfall_config_default(uhsdr_wfall_config* cfg);
+uhsdr_status uhsdr_wfall_plan_build(const uhsdr_wfall_config* cfg, uhsdr_wfall_plan* plan);
+uhsdr_status uhsdr_wfall_create(int32_t num_channels, const uhsdr_wfall_config* cfg, void* stream, uhsdr_wfall_handle* out);
+/* the same with ring and frequencies in host memory, for the _host call (no device call) */
+uhsdr_status uhsdr_wfall_create_host(int32_t num_channels, const uhsdr_wfall_config* cfg, uhsdr_wfall_handle* out);
+uhsdr_status uhsdr_wfall_reset(uhsdr_wfall_handle h);
+uhsdr_status uhsdr_wfall_set_stream(uhsdr_wfall_handle h, void* stream);
+uhsdr_status uhsdr_wfall_process_lines(uhsdr_wfall_handle h, const uint8_t* lines, const uint32_t* center_hz, int32_t frames,
+                                       const uhsdr_wfall_io* io);
+uhsdr_status uhsdr_wfall_process_lines_host(uhsdr_wfall_handle h, const uint8_t* lines, const uint32_t* center_hz, int32_t frames,
+                                            const uhsdr_wfall_io* io);
+/* sd.wfall_line, doubleLineStart and sd.wfall_line_update after everything enqueued; null: not wanted */
+uhsdr_status uhsdr_wfall_state(uhsdr_wfall_handle h, uint32_t* wfall_line, uint32_t* double_line_start, uint32_t* wfall_line_update);
+uhsdr_status uhsdr_wfall_synchronize(uhsdr_wfall_handle h);
+uhsdr_status uhsdr_wfall_destroy(uhsdr_wfall_handle h);
+int32_t      uhsdr_sizeof_wfall_config(void);
+int32_t      uhsdr_sizeof_wfall_plan(void);
 
 #ifdef __cplusplus
 }

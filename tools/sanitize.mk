@@ -1,4 +1,4 @@
-# Host ASan / UBSan build and run of the nine module drivers (tools/*/*_sanitize.c), included by the
+# Host ASan / UBSan build and run of the ten module drivers (tools/*/*_sanitize.c), included by the
 # top-level Makefile:
 #
 #   make sanitize          (objects, programs, their input files and logs under tests/build/sanitize/)
@@ -18,9 +18,9 @@ PYTHON       ?= python3
 
 # program: its directory under tools/, its dump script, the module sources it links (uhsdr_<m>.hip).
 # cwgen takes the text queue's put from digimod, nr's stream can hold a noise blanker; nb_sanitize,
-# meter_sanitize and display_sanitize are plain C over uhsdr_nb.h, uhsdr_meter.h and uhsdr_display.h
-# and link nothing else (the meter's and the display's dump scripts write each case's plan, built
-# through libuhsdr_amd.so).
+# meter_sanitize, display_sanitize and wfall_sanitize are plain C over uhsdr_nb.h, uhsdr_meter.h,
+# uhsdr_display.h and uhsdr_wfall.h and link nothing else (the meter's, the display's and the
+# waterfall's dump scripts write each case's plan, built through libuhsdr_amd.so).
 SAN_cwdec   := cwtext  dump_states.py  cwdec
 SAN_rtty    := rtty    dump_streams.py rtty
 SAN_psk     := psk     dump_streams.py psk
@@ -30,7 +30,8 @@ SAN_nr      := nr      dump_cases.py   nr nb
 SAN_nb      := nb      dump_cases.py
 SAN_meter   := meter   dump_cases.py
 SAN_display := display dump_cases.py
-SAN_PROGS   := cwdec rtty psk digimod cwgen nr nb meter display
+SAN_wfall   := wfall   dump_cases.py
+SAN_PROGS   := cwdec rtty psk digimod cwgen nr nb meter display wfall
 SAN_HOST    := $(SAN)/uhsdr_setup.o $(SAN)/uhsdr_filter_tables.o
 
 sanitize: $(LIB) $(SAN_PROGS:%=$(SAN)/%.log)

@@ -17,7 +17,7 @@ from ._abi import (RxConfig, RxPlan, build_plan, plan_supported, plan_fma_ok, co
                    SpectrumConfig, SpectrumPlan, build_spectrum_plan, default_spectrum_config,
                    spectrum_config_from_ref_args,
                    MeterConfig, MeterPlan, MeterIo, DIGITAL_MODE_NONE, DIGITAL_MODE_RTTY, DIGITAL_MODE_BPSK,
-                   DisplayConfig, DisplayPlan, DisplayIo)
+                   DisplayConfig, DisplayPlan, DisplayIo, WfallConfig, WfallPlan, WfallIo)
 from .rx import RxChain  # noqa: F401
 from .tx import TxChain  # noqa: F401
 from .spectrum import Spectrum  # noqa: F401
@@ -32,3 +32,4 @@ from .nr import NrProcessor, nr_config, nr_band  # noqa: F401
 from .nb import NbProcessor, nb_config  # noqa: F401
 from .meter import Meter, meter_config, meter_plan  # noqa: F401
 from .display import Display, display_config, display_plan  # noqa: F401
+from .wfall import Waterfall, wfall_config, wfall_plan  # noqa: F401

@@ -220,6 +220,26 @@ class DisplayIo(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("scope", "wfall", "offset", "min")]
 
 
+WFALL_COLOURS, WFALL_MAX_MARKER, WFALL_MAX_LINES = 65, 3, 80     # UHSDR_WFALL_COLOURS, _MAX_MARKER, _MAX_LINES
+
+
+class WfallConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "width", "height", "color_scheme", "vert_step_size", "marker_colour", "magnify", "iq_freq_mode", "dmod_mode", "digital_mode",
+        "cw_lsb", "digi_lsb", "cw_sidetone_freq", "rtty_shift_idx", "psk_speed_idx", "tx_minus_rx_hz")] + [("reserved", C.c_int32 * 9)]
+
+
+class WfallPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "wfall_size", "repeat", "vert_step_size", "marker_num")] + [
+        ("hz_per_pixel", C.c_float), ("rx_carrier_pos", C.c_float), ("marker_pos", C.c_float * WFALL_MAX_MARKER),
+        ("marker_pixel", C.c_uint16 * WFALL_MAX_MARKER), ("colours", C.c_uint16 * WFALL_COLOURS), ("reserved", C.c_int32 * 8)]
+
+
+class WfallIo(C.Structure):
+    """uhsdr_wfall_io: optional outputs, 0: not wanted"""
+    _fields_ = [(n, C.c_void_p) for n in ("image", "drawn")]
+
+
 # every exported entry point of include/uhsdr.h: name -> (restype, argtypes)
 SIGNATURES = {
     "uhsdr_rx_config_default": (None, [C.POINTER(RxConfig)]),
@@ -418,6 +438,19 @@ SIGNATURES = {
     "uhsdr_sizeof_display_config": (C.c_int32, []),
     "uhsdr_sizeof_display_plan": (C.c_int32, []),
     "uhsdr_spectrum_set_display": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DisplayIo)]),
+    "uhsdr_wfall_config_default": (None, [C.POINTER(WfallConfig)]),
+    "uhsdr_wfall_plan_build": (C.c_int, [C.POINTER(WfallConfig), C.POINTER(WfallPlan)]),
+    "uhsdr_wfall_create": (C.c_int, [C.c_int32, C.POINTER(WfallConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "uhsdr_wfall_create_host": (C.c_int, [C.c_int32, C.POINTER(WfallConfig), C.POINTER(C.c_void_p)]),
+    "uhsdr_wfall_reset": (C.c_int, [C.c_void_p]),
+    "uhsdr_wfall_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "uhsdr_wfall_process_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(WfallIo)]),
+    "uhsdr_wfall_process_lines_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(WfallIo)]),
+    "uhsdr_wfall_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhsdr_wfall_synchronize": (C.c_int, [C.c_void_p]),
+    "uhsdr_wfall_destroy": (C.c_int, [C.c_void_p]),
+    "uhsdr_sizeof_wfall_config": (C.c_int32, []),
+    "uhsdr_sizeof_wfall_plan": (C.c_int32, []),
     "uhsdr_tx_set_cw_keyer": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "uhsdr_tx_cw_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
     "uhsdr_tx_cw_put_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -483,6 +516,8 @@ def load(path: str | None = None) -> C.CDLL:
         raise RuntimeError("ctypes layout of uhsdr_meter_config / _plan does not match include/uhsdr.h")
     if not variant and (lib.uhsdr_sizeof_display_config() != C.sizeof(DisplayConfig) or lib.uhsdr_sizeof_display_plan() != C.sizeof(DisplayPlan)):
         raise RuntimeError("ctypes layout of uhsdr_display_config / _plan does not match include/uhsdr.h")
+    if not variant and (lib.uhsdr_sizeof_wfall_config() != C.sizeof(WfallConfig) or lib.uhsdr_sizeof_wfall_plan() != C.sizeof(WfallPlan)):
+        raise RuntimeError("ctypes layout of uhsdr_wfall_config / _plan does not match include/uhsdr.h")
     if path is None:
         _lib = lib
     return lib

@@ -1111,3 +1111,142 @@ uhsdr_status uhsdr_display_plan_build(const uhsdr_display_config* cfg, uhsdr_dis
 
 int32_t uhsdr_sizeof_display_config(void) { return (int32_t)sizeof(uhsdr_display_config); }
 int32_t uhsdr_sizeof_display_plan(void) { return (int32_t)sizeof(uhsdr_display_plan); }
+
+/* ---- waterfall image: what UiSpectrum_InitSpectrumDisplayData (ui_spectrum.c:990-1070) and
+   UiSpectrum_UpdateSpectrumPixelParameters (:244-350) compute for UiSpectrum_DrawWaterfall ---- */
+#include "uhsdr_wfall.h"
+#include "uhsdr_wfall_tables.h"
+
+#define WFALL_RTTY_MARK 915                 /* :312 */
+
+void uhsdr_wfall_config_default(uhsdr_wfall_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->width = 256;                            /* the 320 x 240 panel: ui_lcd_layouts.c */
+    cfg->height = 70;                            /* WATERFALL_HEIGHT, ui_lcd_layouts.h:21 */
+    cfg->vert_step_size = 2;                     /* WATERFALL_STEP_SIZE_DEFAULT, ui_spectrum.h:82 */
+    cfg->marker_colour = 0xFFFF;                 /* White, the first entry of the menu's colour table */
+    cfg->iq_freq_mode = UHSDR_IQ_CONV_M12KHZ;    /* as uhsdr_rx_config_default */
+    cfg->dmod_mode = UHSDR_DEMOD_USB;
+    cfg->cw_sidetone_freq = 750;
+    cfg->rtty_shift_idx = 1;                     /* RTTY_SHIFT_170, rtty.c:204 */
+}
+
+uhsdr_status uhsdr_wfall_plan_build(const uhsdr_wfall_config* cfg, uhsdr_wfall_plan* p)
+{
+    /* rtty_shifts[].value (rtty.c:192-200) and psk_speeds[].value (psk.c:417-422) */
+    static const float rtty_shift[6] = { 85, 170, 200, 425, 450, 850 };
+    static const float psk_speed[3] = { 31.25, 62.5, 125.0 };
+    if (!cfg || !p) { uhsdr_set_error("null argument"); return UHSDR_ARGUMENT_ERROR; }
+    const int W = cfg->width, H = cfg->height;
+    if (W < 128 || W > UHSDR_DISPLAY_MAX_WIDTH)
+    { uhsdr_set_error("wfall: width %d outside 128..%d (what the display stage writes)", W, UHSDR_DISPLAY_MAX_WIDTH); return UHSDR_ARGUMENT_ERROR; }
+    if (H < 1 || H > WFALL_MAX_HEIGHT)
+    { uhsdr_set_error("wfall: height %d outside 1..%d", H, WFALL_MAX_HEIGHT); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->color_scheme < 0 || cfg->color_scheme > 4)
+    { uhsdr_set_error("wfall: color_scheme %d outside 0..4", cfg->color_scheme); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->vert_step_size < 1 || cfg->vert_step_size > 5)
+    { uhsdr_set_error("wfall: vert_step_size %d outside 1..5 (WATERFALL_STEP_SIZE_MIN..MAX)", cfg->vert_step_size); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->marker_colour < 0 || cfg->marker_colour > 0xFFFF)
+    { uhsdr_set_error("wfall: marker_colour %d is no RGB565 value", cfg->marker_colour); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->magnify < 0 || cfg->magnify > 5)
+    { uhsdr_set_error("wfall: magnify %d outside 0..5 (MAGNIFY_MIN..MAGNIFY_MAX)", cfg->magnify); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->iq_freq_mode < UHSDR_IQ_CONV_OFF || cfg->iq_freq_mode > UHSDR_IQ_CONV_M12KHZ)
+    { uhsdr_set_error("wfall: iq_freq_mode %d unknown", cfg->iq_freq_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->dmod_mode < UHSDR_DEMOD_USB || cfg->dmod_mode > UHSDR_DEMOD_IQ)
+    { uhsdr_set_error("wfall: dmod_mode %d unknown", cfg->dmod_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->digital_mode < UHSDR_DIGITAL_MODE_NONE || cfg->digital_mode > UHSDR_DIGITAL_MODE_BPSK)
+    { uhsdr_set_error("wfall: digital_mode %d unknown", cfg->digital_mode); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->cw_lsb < 0 || cfg->cw_lsb > 1 || cfg->digi_lsb < 0 || cfg->digi_lsb > 1)
+    { uhsdr_set_error("wfall: cw_lsb %d / digi_lsb %d outside 0..1", cfg->cw_lsb, cfg->digi_lsb); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->cw_sidetone_freq < 0 || cfg->cw_sidetone_freq > 65535)
+    { uhsdr_set_error("wfall: cw_sidetone_freq %d out of range", cfg->cw_sidetone_freq); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->rtty_shift_idx < 0 || cfg->rtty_shift_idx > 5)
+    { uhsdr_set_error("wfall: rtty_shift_idx %d outside 0..5", cfg->rtty_shift_idx); return UHSDR_ARGUMENT_ERROR; }
+    if (cfg->psk_speed_idx < 0 || cfg->psk_speed_idx > 2)
+    { uhsdr_set_error("wfall: psk_speed_idx %d outside 0..2", cfg->psk_speed_idx); return UHSDR_ARGUMENT_ERROR; }
+
+    /* :1041-1070 */
+    int size = H;
+    if (size * W > UHSDR_WFALL_RING_BYTES)
+    {
+        if (size / 2 * W > UHSDR_WFALL_RING_BYTES) size = UHSDR_WFALL_RING_BYTES / W;
+        else size /= 2;
+    }
+    if (size < 1 || size > UHSDR_WFALL_MAX_LINES)
+    {
+        uhsdr_set_error("wfall: %d x %d keeps %d ring lines, sd.waterfall_frequencies has %d", W, H, size, UHSDR_WFALL_MAX_LINES);
+        return UHSDR_ARGUMENT_ERROR;
+    }
+    memset(p, 0, sizeof *p);
+    p->width = W;
+    p->height = H;
+    p->wfall_size = size;
+    p->repeat = H / size;
+    p->vert_step_size = cfg->vert_step_size;
+    memcpy(p->colours, uhsdr_wfall_palettes[cfg->color_scheme], sizeof uhsdr_wfall_palettes[0]);
+    p->colours[WFALL_MARKER_ENTRY] = (uint16_t)cfg->marker_colour;
+
+    /* :256-276 */
+    p->hz_per_pixel = (float)IQ_SAMPLE_RATE / ((1 << cfg->magnify) * W);
+    int32_t translate = 0, kind = 0, up = 0;            /* AudioDriver_GetTranslateFreq */
+    float oc = 0, os = 0;
+    shift_plan(cfg->iq_freq_mode, &translate, &kind, &up, &oc, &os);
+    if (!cfg->magnify) p->rx_carrier_pos = W / 2 - 0.5 - (translate / p->hz_per_pixel);
+    else p->rx_carrier_pos = W / 2 - 0.5;
+
+    /* :287-346 */
+    const float tx_vfo_offset = ((float)cfg->tx_minus_rx_hz) / p->hz_per_pixel;
+    float mode_marker_offset[UHSDR_WFALL_MAX_MARKER] = { 0 };
+    switch (cfg->dmod_mode)
+    {
+    case UHSDR_DEMOD_CW:
+        mode_marker_offset[0] = (cfg->cw_lsb ? -1.0 : 1.0) * ((float)cfg->cw_sidetone_freq / p->hz_per_pixel);
+        p->marker_num = 1;
+        break;
+    case UHSDR_DEMOD_DIGI:
+    {
+        float mode_marker[UHSDR_WFALL_MAX_MARKER] = { 0 };
+        switch (cfg->digital_mode)
+        {
+        case UHSDR_DIGITAL_MODE_RTTY:
+            mode_marker[0] = WFALL_RTTY_MARK;
+            mode_marker[1] = mode_marker[0] + rtty_shift[cfg->rtty_shift_idx];
+            p->marker_num = 2;
+            break;
+        case UHSDR_DIGITAL_MODE_BPSK:
+            mode_marker[0] = PSK_OFFSET - psk_speed[cfg->psk_speed_idx] / 2;
+            mode_marker[1] = PSK_OFFSET + psk_speed[cfg->psk_speed_idx] / 2;
+            p->marker_num = 2;
+            break;
+        default:
+            mode_marker[0] = 0;
+            p->marker_num = 1;
+        }
+        for (int idx = 0; idx < p->marker_num; idx++) mode_marker_offset[idx] = (cfg->digi_lsb ? -1.0 : 1.0) * (mode_marker[idx] / p->hz_per_pixel);
+        break;
+    }
+    default:
+        mode_marker_offset[0] = 0;
+        p->marker_num = 1;
+    }
+    for (int idx = 0; idx < UHSDR_WFALL_MAX_MARKER; idx++)
+    {
+        if (idx < p->marker_num)
+        {
+            const float marker_offset = tx_vfo_offset + mode_marker_offset[idx];
+            p->marker_pos[idx] = p->rx_carrier_pos + marker_offset;
+            p->marker_pixel[idx] = (uint16_t)display_to_bits(p->marker_pos[idx]);     /* :1113 */
+        }
+        else
+        {
+            p->marker_pos[idx] = W;
+            p->marker_pixel[idx] = (uint16_t)W;
+        }
+    }
+    return UHSDR_OK;
+}
+
+int32_t uhsdr_sizeof_wfall_config(void) { return (int32_t)sizeof(uhsdr_wfall_config); }
+int32_t uhsdr_sizeof_wfall_plan(void) { return (int32_t)sizeof(uhsdr_wfall_plan); }
